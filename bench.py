@@ -1,17 +1,21 @@
 #!/usr/bin/env python
 """bench.py -- rays/s of the NeuMan ray-march hot path on MI355X (BASELINE.json metric, config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches itself: it checks that N devices are
-visible (one JSON error line and exit code 2 otherwise) and re-executes under torch.distributed.run with one rank per GPU.
+visible (one JSON error line and exit code 2 otherwise) and runs itself under torch.distributed.run (a child process) with one rank per GPU.
 
 One "step" = one 800x800 frame of the background NeRF: 128 coarse + 128 importance samples per ray (the reference
 evaluates the 8x256 MLP 128 + 256 = 384 times per ray, render_utils.py:108-161), synthetic-dense weights
 (SURVEY 8d), rays already resident in HBM when the timed region starts.  With N > 1 the frame's ray tiles are
 sharded across the ranks (no data-path collective) and assembled on rank 0 by one RCCL gather per frame, which is
 inside the timed region; total work is fixed, so `scaling` is "strong".
+
+`--dump-outputs DIR`: after the timed steps rank 0 writes what the last of them returned -- the frame's per-ray colour and
+depth, as render_vanilla_rays hands them to its caller -- as DIR/rgb.npy [640000, 3] and DIR/depth.npy [640000] in float32.
+The nets are seeded and the rays fixed, so two builds run with the same arguments can be compared output for output.
 
 Precision (`--precision`, default "mixed" = the package default): the coarse pass, whose compositing weights place the
 importance samples, runs split-fp16 x3 (float32-class sigma: the inverse CDF amplifies a coarse-pass error by 1 / pdf);
@@ -42,6 +46,7 @@ a bounded prefix of the same frame, on this box's host cores (N = 1 only).
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -303,7 +308,7 @@ def train_iteration(dev, origins, dirs, cap, rays=2048, iters=5):
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` (N > 1) started by hand: become `torch.distributed.run --nproc-per-node N bench.py ...`.
+    """`python bench.py --gpus N` (N > 1) started by hand: run `torch.distributed.run --nproc-per-node N bench.py ...` as a child and exit with its code.
     Returns only on error (after printing one JSON line)."""
     import socket
     n = args.gpus
@@ -321,7 +326,7 @@ def self_launch(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")          # dmabuf IPC: RCCL across processes needs it on this driver
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execvpe(cmd[0], cmd, env)
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)     # a fresh child process, never exec over this one
 
 
 def launch_check(args, rank, world):
@@ -356,6 +361,7 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="process-group backend (nccl = RCCL; gloo only with --launch-check)")
     ap.add_argument("--launch-check", action="store_true", help="bring the process group up, assemble one dummy frame through the gather "
                     "and exit (no device needed with --backend gloo: the CPU-side test of the self-launch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's frame (rgb, depth per ray) as DIR/<name>.npy in float32")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -436,11 +442,19 @@ def main():
             log.clear()
         gather_events.clear()
         sync()
+        frame = None
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            frame = None                                                   # released before the next step, as a discarded result is
+            frame = step()
         sync()
         dt = time.perf_counter() - t0
+    if args.dump_outputs and frame is not None:                            # rank 0's assembled frame (None on the other ranks)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, out in zip(("rgb", "depth"), frame):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), out.to(torch.float32).cpu().numpy())
+    frame = None
     t = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1 or args.dist:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

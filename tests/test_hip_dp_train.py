@@ -48,10 +48,11 @@ def check(rep, world):
         assert abs(a - b) <= 2e-3 * max(abs(a), 1e-3), (rep["curve_full"], rep["curve_dp"])
 
 
-@pytest.mark.parametrize("world", [2, 8])
+@pytest.mark.parametrize("world", [2, 4])
 def test_ranks_share_the_gpu_gradients_over_gloo(world):
-    """world 8 = the node's size: eight shards of every batch, eight normaliser contributions and dead-flag votes in the all_gather, one all_reduce of
-    the flat gradient buffer -- the summed gradient equals the full-batch one"""
+    """world 4: four shards of every batch, four normaliser contributions and dead-flag votes in the all_gather, one all_reduce of
+    the flat gradient buffer -- the summed gradient equals the full-batch one.  (The ranks and this process all hold the one GPU, which
+    takes at most six processes at once: the node's size, 8, runs its collectives on CPU in tests/test_dp_gloo.py.)"""
     port = free_port()
     procs = [subprocess.Popen([sys.executable, os.path.join(HERE, "helpers", "dist_train_check.py"), "gloo"], env=env_for(r, world, port),
                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(world)]

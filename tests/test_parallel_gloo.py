@@ -134,7 +134,7 @@ def test_world_size_one_needs_no_process_group():
 
 @pytest.mark.parametrize("n", [2, 8])
 def test_bench_launches_itself_at_n_gt_1(n):
-    """`python bench.py --gpus N` with no WORLD_SIZE in the environment re-executes under torch.distributed.run, all ranks reach
+    """`python bench.py --gpus N` with no WORLD_SIZE in the environment runs itself under torch.distributed.run in a child process, all ranks reach
     init_process_group and assemble a frame through parallel.gather_frame (gloo + host tensors: what runs without GPUs); N = 8 is
     the driver's own launch at the node's size."""
     import json

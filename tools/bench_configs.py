@@ -17,6 +17,7 @@ import argparse
 import json
 import os
 import socket
+import subprocess
 import sys
 import time
 
@@ -42,7 +43,7 @@ def self_launch(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execvpe(cmd[0], cmd, env)
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)     # a fresh child process, never exec over this one
 
 
 def main():

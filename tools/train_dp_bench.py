@@ -11,6 +11,7 @@ backward, the gradient all_reduce, Adam -- between barriers, the maximum over th
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 import types
@@ -36,7 +37,7 @@ def self_launch(args):
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execvpe(cmd[0], cmd, env)
+    raise SystemExit(subprocess.run(cmd, env=env).returncode)     # a fresh child process, never exec over this one
 
 
 def main():
