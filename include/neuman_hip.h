@@ -254,6 +254,38 @@ int nm_mlp_forward_ray_chunk(nm_mlp_t mlp, const float* origin, const float* dir
 int nm_mlp_sigma_ray_chunk(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int S_total,
                            const int32_t* ray_idx, const int32_t* n_rays_dev, int64_t n_rays, int s0, int S, int precision,
                            float sigma_scale, float* out, nm_stream_t stream);
+/* ---------------------------------------------------------------------------------------------
+ * K11  occupancy-grid empty-space skipping for the background passes -- reference utils/render_utils.py:131-151, 287-297 (which
+ * evaluate every sample).  A skipped sample keeps raw = 0: alpha = 0 and weight 0 in raw2outputs, exactly what a sample with
+ * relu(sigma) = 0 gets.  Grid: res^3 bits (res 4..256, a multiple of 4) over the box aabb = host float[6] (lo x y z, hi x y z);
+ * cell (i, j, k) along (x, y, z) is bit c = (k res + j) res + i of word c >> 5.  Every buffer is the caller's.
+ *
+ * nm_occ_probe_offset: offset in [0, 1) along `axis` of probe k inside every cell (a sub-cell lattice of m^3 >= probes slots with a
+ *   seeded jitter); the probe of cell (i, j, k) is lo + (float(i) + offset) * ((hi - lo) / res) per axis, in float32.
+ * nm_occ_build: cell value = max sigma of the net (density-only launch, `precision`) over its probes; a cell is occupied when a cell
+ *   within `dilate` of it per axis has a value > sigma_threshold (>= 0).  workspace: nm_occ_build_workspace_floats(res, probes)
+ *   floats (16-byte aligned); bits: res^3 / 32 words.
+ * nm_occ_compact_samples: sample_idx [R*S] receives the ascending flat indices r*S + s of the samples of rays origin + direction *
+ *   z_vals [R,S] (the point built as the MLP launches build it) whose cell is occupied or that lie outside the box; counts[0] =
+ *   their number, counts[1] = the skipped (device int32[2]).  workspace: nm_occ_compact_workspace_ints(R*S) int32.
+ * nm_mlp_forward_samples / nm_mlp_sigma_samples: nm_mlp_forward_rays / nm_mlp_sigma_rays on the listed samples only (in_mode 3):
+ *   the first *n_dev entries of sample_idx (n_dev nullable: n_max entries; n_max = the list's upper bound) are evaluated and written
+ *   into out[r, s] [R,S,4]; nothing else of out is touched.  Bit-identical to the matching records of the every-sample launch.
+ *   NM_PREC_FP32 is not available in this form.
+ * ------------------------------------------------------------------------------------------- */
+float nm_occ_probe_offset(int probes, int seed, int k, int axis);
+int64_t nm_occ_build_workspace_floats(int res, int probes);
+int nm_occ_build(nm_mlp_t mlp, const float* aabb, int res, int probes, int dilate, float sigma_threshold, int seed, int precision,
+                 float* workspace, int64_t workspace_floats, uint32_t* bits, nm_stream_t stream);
+int64_t nm_occ_compact_workspace_ints(int64_t n_samples);
+int nm_occ_compact_samples(const uint32_t* bits, int res, const float* aabb, const float* origin, const float* direction, const float* z_vals,
+                           int64_t R, int S, int32_t* sample_idx, int32_t* counts, int32_t* workspace, nm_stream_t stream);
+int nm_mlp_forward_samples(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S,
+                           const int32_t* sample_idx, const int32_t* n_dev, int64_t n_max, int precision, float sigma_scale, float* out,
+                           nm_stream_t stream);
+int nm_mlp_sigma_samples(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S,
+                         const int32_t* sample_idx, const int32_t* n_dev, int64_t n_max, int precision, float sigma_scale, float* out,
+                         nm_stream_t stream);
 /* T[r] *= prod_{i in chunk} (1 - alpha_i + 1e-10) for the listed rays (ray_idx nullable = rays 0..n_rays-1): the
  * transmittance factors of raw2outputs (render_utils.py:85-95) over samples s0 .. s0+S-1 of raw [R,S_total,4]; rays whose T
  * falls below the caller's epsilon are dropped by nm_compact_hits(eps, T). */

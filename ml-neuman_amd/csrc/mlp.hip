@@ -27,7 +27,8 @@ namespace {
 // in-order counter: the launch took 1578.0 / 1580.2 us against 1573.8 / 1582.9 -- no effect; profiles/r06_train_experiments.md.)
 template <int PREC, bool PROF, int SAVE = 0>
 __global__ __launch_bounds__(kThreads, 2) void nerf_mlp_kernel(const MlpArgs a_in) {
-    const MlpArgs a = resolve_args(a_in);
+    // (the SAVE forms are launched on given points only, nm_mlp_forward_save*: in_mode pinned, the ray forms are not compiled into them)
+    const MlpArgs a = [&] { MlpArgs t = resolve_args(a_in); if (SAVE) t.in_mode = 0; return t; }();
     unsigned long long pr[6] = {0, 0, 0, 0, 0, 0};
     unsigned long long t_prev = PROF ? __builtin_readcyclecounter() : 0;
 #define NM_TICK(b)                                                   \

@@ -939,6 +939,31 @@ int nm_mlp_sigma_ray_chunk(nm_mlp_t mlp, const float* origin, const float* direc
                         nullptr, stream, nullptr, 1, &c);
 }
 
+static int forward_samples(const char* what, int sigma_only, nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R,
+                           int S, const int32_t* sample_idx, const int32_t* n_dev, int64_t n_max, int precision, float sigma_scale, float* out,
+                           nm_stream_t stream) {
+    NM_REQUIRE(n_max == 0 || (origin && direction && z_vals && sample_idx && out), "%s: null pointer", what);
+    NM_REQUIRE(R >= 0 && S >= 1 && n_max >= 0 && n_max <= R * (int64_t)S && R * (int64_t)S < (1ll << 31), "%s: bad sizes (R=%lld S=%d n_max=%lld)", what,
+               (long long)R, S, (long long)n_max);
+    NM_REQUIRE(precision != NM_PREC_FP32, "%s: the exact-f32 validation kernel has no sample-list form", what);
+    NM_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "%s: out must be 16-byte aligned", what);
+    nm::MlpChunk c{sample_idx, n_dev, 0, S};
+    return mlp_dispatch(mlp, nullptr, nullptr, origin, direction, z_vals, n_max, S, 3, precision, -2, sigma_scale, out, nullptr, stream, nullptr,
+                        sigma_only, &c);
+}
+
+int nm_mlp_forward_samples(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S,
+                           const int32_t* sample_idx, const int32_t* n_dev, int64_t n_max, int precision, float sigma_scale, float* out,
+                           nm_stream_t stream) {
+    return forward_samples("nm_mlp_forward_samples", 0, mlp, origin, direction, z_vals, R, S, sample_idx, n_dev, n_max, precision, sigma_scale, out, stream);
+}
+
+int nm_mlp_sigma_samples(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S,
+                         const int32_t* sample_idx, const int32_t* n_dev, int64_t n_max, int precision, float sigma_scale, float* out,
+                         nm_stream_t stream) {
+    return forward_samples("nm_mlp_sigma_samples", 1, mlp, origin, direction, z_vals, R, S, sample_idx, n_dev, n_max, precision, sigma_scale, out, stream);
+}
+
 int nm_mlp_forward_profile(nm_mlp_t mlp, const float* pts, const float* dirs, int64_t n, int precision, float* out,
                            uint64_t* cycles, nm_stream_t stream) {
     NM_REQUIRE(n == 0 || (pts && dirs && out && cycles), "nm_mlp_forward_profile: null pointer");

@@ -33,7 +33,8 @@ struct RefLaunch {
 };
 
 // in_mode 2: the launch covers samples s0 .. s0 + S - 1 of the rays listed in ray_idx (n = upper bound of listed rays * S; the
-// actual list length is read from *n_rays_dev on the device when that is non-null); z and out are [R, S_total] (x4)
+// actual list length is read from *n_rays_dev on the device when that is non-null); z and out are [R, S_total] (x4).
+// in_mode 3: ray_idx lists flat sample indices r * S + s of z [R, S] (n = upper bound, *n_rays_dev the length; s0 = 0, S_total = S)
 struct MlpChunk {
     const int* ray_idx; const int* n_rays_dev; int s0, S_total;
 };

@@ -40,6 +40,13 @@ SIGNATURES = {
     "nm_importance_z": (i32, [c_f32p, c_f32p, i64, i32, c_f32p, i32, i32, c_f32p, c_stream]),
     "nm_near_far": (i32, [c_f32p, c_f32p, i64, c_f32p, i32, ctypes.c_double, c_f32p, c_f32p, c_stream]),
     "nm_compact_workspace_ints": (i64, [i64]),
+    "nm_occ_probe_offset": (ctypes.c_float, [i32, i32, i32, i32]),
+    "nm_occ_build_workspace_floats": (i64, [i32, i32]),
+    "nm_occ_build": (i32, [ctypes.c_void_p, ctypes.c_void_p, i32, i32, i32, ctypes.c_float, i32, i32, c_f32p, i64, c_i32p, c_stream]),
+    "nm_occ_compact_workspace_ints": (i64, [i64]),
+    "nm_occ_compact_samples": (i32, [c_i32p, i32, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, c_i32p, c_i32p, c_i32p, c_stream]),
+    "nm_mlp_forward_samples": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, c_i32p, c_i32p, i64, i32, ctypes.c_float, c_f32p, c_stream]),
+    "nm_mlp_sigma_samples": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, c_i32p, c_i32p, i64, i32, ctypes.c_float, c_f32p, c_stream]),
     "nm_compact_hits": (i32, [c_f32p, c_f32p, i64, c_i32p, c_i32p, c_i32p, c_i32p, c_stream]),
     "nm_mlp_pack_bytes": (i64, [ctypes.POINTER(MlpDesc)]),
     "nm_mlp_pack_i8s_bytes": (i64, [ctypes.POINTER(MlpDesc)]),

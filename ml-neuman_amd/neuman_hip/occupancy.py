@@ -1,0 +1,196 @@
+"""Occupancy-grid empty-space skipping for the background passes (csrc/occupancy.hip).
+
+The reference evaluates every sample of every ray (utils/render_utils.py:131-151, 287-297).  A net with a grid attached
+(`attach`) has its background passes -- render_utils.bkg_place_z / bkg_shade, i.e. render_vanilla, render_hybrid_nerf,
+render_hybrid_nerf_multi_persons and the sharded frame path -- evaluate only the samples whose cell is occupied (or that lie
+outside the grid's box); the others keep raw = 0, which raw2outputs turns into alpha = 0 and weight 0, exactly what a sample
+with relu(sigma) = 0 gets.  On every ray whose skipped samples all have relu(sigma) = 0 in the every-sample evaluation the
+frame, its depth and the coarse weights (so the importance samples) are therefore bit-identical.  Off by default: with no grid
+attached nothing changes.
+
+    grid = OccupancyGrid.from_net(coarse, aabb=((-2, -2, -4), (2, 2, 0)))
+    attach(coarse, grid); attach(fine, OccupancyGrid.from_net(fine, aabb=...))
+
+Cells: `res`^3 over the box, cell (i, j, k) along (x, y, z); masks are boolean tensors indexed [i, j, k].
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+
+_ATTR = '_occupancy_grid'
+
+
+def probe_offsets(probes, seed):
+    """[probes, 3] float32: the sub-cell offsets in [0, 1) of the probes, the same in every cell (nm_occ_probe_offset)."""
+    L = _lib.lib()
+    return torch.tensor([[L.nm_occ_probe_offset(int(probes), int(seed), k, a) for a in range(3)] for k in range(int(probes))], dtype=torch.float32)
+
+
+def _check_box(aabb):
+    box = torch.as_tensor(aabb, dtype=torch.float32).reshape(-1).cpu()
+    if box.numel() != 6 or not bool(torch.isfinite(box).all()) or not bool((box[:3] < box[3:]).all()):
+        raise ValueError(f"aabb must be (lo xyz, hi xyz) with finite lo < hi on every axis, got {box.tolist()}")
+    return box
+
+
+def _check_res(res):
+    res = int(res)
+    if not (4 <= res <= 256 and res % 4 == 0):
+        raise ValueError(f"res must be a multiple of 4 in 4..256, got {res}")
+    return res
+
+
+def _refuse_time_net(net):
+    if getattr(getattr(net, 'pos_pe', None), 'input_dims', 3) != 3:
+        raise NotImplementedError("occupancy grids serve static background nets only: the time-conditioned net (raw_pos_dim = 4, "
+                                  "--ablate_nerft) has no fixed density field to grid")
+
+
+def rays_aabb(o, d, near, far, pad=1e-3):
+    """The smallest box holding every sample of rays o + d z, z in [near, far] (their end points: the passes' samples lie on the
+    segments between them), grown by `pad` of its extent per side -> (lo xyz, hi xyz) float32 on the host."""
+    o, d = o.reshape(-1, 3).float(), d.reshape(-1, 3).float()
+    near = torch.as_tensor(near, dtype=torch.float32, device=o.device).reshape(-1, 1)
+    far = torch.as_tensor(far, dtype=torch.float32, device=o.device).reshape(-1, 1)
+    ends = torch.cat([o + d * near, o + d * far], 0)
+    lo, hi = ends.min(0).values.cpu(), ends.max(0).values.cpu()
+    g = (hi - lo).clamp_min(1e-6) * pad
+    return torch.cat([lo - g, hi + g])
+
+
+class OccupancyGrid:
+    """res^3 occupancy bits over an axis-aligned box: `bits` int32 [res^3 / 32] (bit c = (k res + j) res + i of word c >> 5)."""
+
+    def __init__(self, aabb, res, bits, meta=None):
+        self.aabb = _check_box(aabb)
+        self.res = _check_res(res)
+        bits = torch.as_tensor(bits)
+        if bits.dtype != torch.int32 or bits.numel() != self.res ** 3 // 32:
+            raise ValueError(f"bits must be int32 [{self.res ** 3 // 32}], got {bits.dtype} [{bits.numel()}]")
+        self.bits = bits.reshape(-1).contiguous()
+        self.meta = dict(meta or {})
+
+    # ---- construction ---------------------------------------------------------------------
+    @classmethod
+    def from_net(cls, net, aabb, res=128, probes=8, dilate=1, sigma_threshold=0.0, seed=0, precision=None):
+        """Cell occupied <=> some cell within `dilate` of it (per axis) has max sigma > sigma_threshold over its `probes` points
+        (probe_offsets), evaluated by the net's density-only launch at the precision of its coarse pass (role None)."""
+        _refuse_time_net(net)
+        box, res = _check_box(aabb), _check_res(res)
+        if not 1 <= int(probes) <= 64:
+            raise ValueError(f"probes must be in 1..64, got {probes}")
+        if not 0 <= int(dilate) <= 8:
+            raise ValueError(f"dilate must be in 0..8, got {dilate}")
+        if not float(sigma_threshold) >= 0.0:
+            raise ValueError(f"sigma_threshold must be >= 0, got {sigma_threshold}")
+        net._guard()
+        dev = next(net.parameters()).device
+        L = _lib.lib()
+        ws = torch.empty(int(L.nm_occ_build_workspace_floats(res, int(probes))), device=dev, dtype=torch.float32)
+        bits = torch.empty(res ** 3 // 32, device=dev, dtype=torch.int32)
+        box_c = (ctypes.c_float * 6)(*box.tolist())
+        with torch.no_grad():
+            _lib.check(L.nm_occ_build(net.handle(), box_c, res, int(probes), int(dilate), float(sigma_threshold), int(seed),
+                                      net._prec(precision, None), _lib.dev_ptr(ws), ws.numel(), _lib.dev_ptr(bits, torch.int32),
+                                      _lib.stream_ptr()), "nm_occ_build")
+        return cls(box, res, bits, dict(source='net', probes=int(probes), dilate=int(dilate), sigma_threshold=float(sigma_threshold), seed=int(seed)))
+
+    @classmethod
+    def from_mask(cls, aabb, mask, device=None):
+        """A user-supplied occupancy (e.g. from the COLMAP points): bool [res, res, res] indexed [i, j, k] along (x, y, z)."""
+        mask = torch.as_tensor(mask)
+        if mask.dtype != torch.bool or mask.dim() != 3 or len(set(mask.shape)) != 1:
+            raise ValueError(f"mask must be a cubic bool tensor [res, res, res], got {mask.dtype} {tuple(mask.shape)}")
+        res = _check_res(mask.shape[0])
+        flat = mask.permute(2, 1, 0).reshape(-1, 32).to(torch.int64)                 # cell c = (k res + j) res + i
+        words = (flat << torch.arange(32, dtype=torch.int64, device=flat.device)).sum(dim=1)
+        words = torch.where(words >= 1 << 31, words - (1 << 32), words).to(torch.int32)
+        dev = device if device is not None else (mask.device if mask.is_cuda else None)
+        return cls(aabb, res, words.to(dev) if dev is not None else words, dict(source='mask'))
+
+    # ---- inspection / persistence -----------------------------------------------------------
+    def to_mask(self):
+        """bool [res, res, res] indexed [i, j, k]."""
+        w = self.bits.to(torch.int64) & 0xffffffff
+        b = ((w[:, None] >> torch.arange(32, dtype=torch.int64, device=w.device)) & 1).bool()
+        return b.reshape(self.res, self.res, self.res).permute(2, 1, 0).contiguous()
+
+    def occupied_fraction(self):
+        w = self.bits.to(torch.int64) & 0xffffffff
+        n = int(((w[:, None] >> torch.arange(32, dtype=torch.int64, device=w.device)) & 1).sum())
+        return n / self.res ** 3
+
+    def to(self, device):
+        return OccupancyGrid(self.aabb, self.res, self.bits.to(device), self.meta)
+
+    def state_dict(self):
+        return {'aabb': self.aabb.clone(), 'res': self.res, 'bits': self.bits.cpu().clone(), 'meta': dict(self.meta)}
+
+    @classmethod
+    def from_state_dict(cls, sd, device=None):
+        bits = sd['bits'] if device is None else sd['bits'].to(device)
+        return cls(sd['aabb'], int(sd['res']), bits, sd.get('meta'))
+
+    # ---- the sample list of a pass ----------------------------------------------------------
+    def compact(self, o, d, z):
+        """-> (sample_idx int32 [R*S]: flat indices r*S + s of the samples to evaluate, ascending, the first counts[0] live;
+        counts int32 [2] = (evaluated, skipped)), both on the device"""
+        R, S = z.shape
+        dev = z.device
+        if self.bits.device != dev:
+            raise _lib.NeumanHipError(f"the grid lives on {self.bits.device}, the rays on {dev}: attach() the grid to the net on its device")
+        idx = torch.empty(R * S, device=dev, dtype=torch.int32)
+        counts = torch.zeros(2, device=dev, dtype=torch.int32)
+        L = _lib.lib()
+        ws = torch.empty(int(L.nm_occ_compact_workspace_ints(R * S)), device=dev, dtype=torch.int32)
+        _lib.check(L.nm_occ_compact_samples(_lib.dev_ptr(self.bits, torch.int32), self.res, (ctypes.c_float * 6)(*self.aabb.tolist()),
+                                            _lib.dev_ptr(o, name='origin'), _lib.dev_ptr(d, name='direction'), _lib.dev_ptr(z, name='z_vals'),
+                                            R, S, _lib.dev_ptr(idx, torch.int32), _lib.dev_ptr(counts, torch.int32), _lib.dev_ptr(ws, torch.int32),
+                                            _lib.stream_ptr()), "nm_occ_compact_samples")
+        return idx, counts
+
+
+def attach(net, grid):
+    """Give `net` (a background Joiner) an occupancy grid: its background passes skip the grid's empty cells from now on.
+    Coarse and fine nets have different densities: each gets its own grid (the same object may serve a net used for both)."""
+    _refuse_time_net(net)
+    if not isinstance(grid, OccupancyGrid):
+        raise TypeError(f"attach() takes an OccupancyGrid, got {type(grid).__name__}")
+    dev = next(net.parameters()).device
+    setattr(net, _ATTR, grid if grid.bits.device == dev else grid.to(dev))
+    return net
+
+
+def detach(net):
+    """Remove the net's grid (every sample is evaluated again)."""
+    if hasattr(net, _ATTR):
+        delattr(net, _ATTR)
+    return net
+
+
+def grid_of(net):
+    return getattr(net, _ATTR, None) if net is not None else None
+
+
+def forward_rays(net, o, d, z, precision=None, role=None, sigma_only=False, stats=None):
+    """net.forward_rays over the grid's occupied samples only: raw [R,S,4], zero on every skipped sample.  `stats` (a dict)
+    receives 'evaluated' / 'total' sample counts (one host read)."""
+    grid = grid_of(net)
+    net._guard(o, d, z)
+    o, d, z = o.contiguous(), d.contiguous(), z.contiguous()
+    R, S = z.shape
+    raw = torch.zeros((R, S, 4), device=z.device, dtype=torch.float32)
+    if R == 0:
+        return raw
+    idx, counts = grid.compact(o, d, z)
+    L = _lib.lib()
+    entry = L.nm_mlp_sigma_samples if sigma_only else L.nm_mlp_forward_samples
+    _lib.check(entry(net.handle(), _lib.dev_ptr(o, name='origin'), _lib.dev_ptr(d, name='direction'), _lib.dev_ptr(z, name='z_vals'), R, S,
+                     _lib.dev_ptr(idx, torch.int32), _lib.dev_ptr(counts, torch.int32), R * S, net._prec(precision, role), 1.0,
+                     _lib.dev_ptr(raw), _lib.stream_ptr()), "nm_mlp_sigma_samples" if sigma_only else "nm_mlp_forward_samples")
+    if stats is not None:
+        stats['evaluated'] = stats.get('evaluated', 0) + int(counts[0].item())
+        stats['total'] = stats.get('total', 0) + R * S
+    return raw

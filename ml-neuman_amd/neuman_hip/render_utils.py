@@ -20,7 +20,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, parallel, ray_utils
+from . import _lib, occupancy, parallel, ray_utils
 from .ray_utils import DEFAULT_GEO_THRESH
 
 MAX_RAYS_PER_LAUNCH = int(os.environ.get("NEUMAN_MAX_RAYS_PER_LAUNCH", 1 << 20))
@@ -270,6 +270,10 @@ def bkg_pass_rays_fused(coarse_net, fine_net, o, d, near, far, samples_per_ray, 
     fine pass, enqueued back to back; same kernels, same bits).  What the trainers' frozen background evaluation uses: at 2048 rays
     the five launches are shorter than the Python between them."""
     _lib.require_gpu()
+    if _occupancy_on(coarse_net, fine_net):                # the fused call evaluates every sample: a grid takes the unfused passes
+        raw, z = bkg_pass_rays(coarse_net, fine_net, o.contiguous(), d.contiguous(), near.reshape(-1).contiguous(), far.reshape(-1).contiguous(),
+                               samples_per_ray, importance_samples_per_ray, white_bkg, precision)
+        return raw, z
     R, S = o.shape[0], int(samples_per_ray)
     N = int(importance_samples_per_ray) if fine_net is not None else 0
     dev = o.device
@@ -290,11 +294,37 @@ def bkg_pass_rays_fused(coarse_net, fine_net, o, d, near, far, samples_per_ray, 
     return raw, z
 
 
+def _occupancy_on(*nets):
+    """Does a background pass of these nets skip empty space (occupancy.attach)?  Refuses the combination with early termination."""
+    on = any(occupancy.grid_of(n_) is not None for n_ in nets)
+    if on and TERMINATION_EPS > 0:
+        raise NotImplementedError("an occupancy grid together with early ray termination (TERMINATION_EPS > 0) is not served: "
+                                  "detach the grid or set TERMINATION_EPS = 0")
+    return on
+
+
+def _occupancy_pass(net, o, d, z, precision, role, sigma_only, trace, key):
+    """net.forward_rays on the samples its grid keeps (occupancy.forward_rays); `trace` receives {key: {'evaluated', 'total'}}."""
+    stats = {} if trace is not None else None
+    raw = occupancy.forward_rays(net, o, d, z, precision=precision, role=role, sigma_only=sigma_only, stats=stats)
+    _note(trace, **{key: stats})
+    return raw
+
+
 def bkg_place_z(coarse_net, fine_net, o, d, near, far, samples_per_ray, importance_samples_per_ray, white_bkg, precision=None, trace=None):
     """Where the background list's FINAL samples are (render_utils.py:131-147, 287-293): the stratified samples, or -- with a fine net --
     the coarse density pass, its compositing weights and the importance samples merged in.  -> (z [R,S'], raw of the coarse pass when it
     is the pass that is composited [no fine net; evaluated here unless termination is on], else None)"""
+    occ = _occupancy_on(coarse_net)
     _, _, z = ray_utils.sample_z(o, d, near, far, samples_per_ray)
+    if occ:
+        # empty-space skipping (occupancy.py): skipped samples keep raw = 0 -- weight 0, as relu(sigma) = 0 gives
+        if fine_net is None:
+            return z, _occupancy_pass(coarse_net, o, d, z, precision, 'shading', False, trace, 'occupancy_coarse')
+        raw = _occupancy_pass(coarse_net, o, d, z, precision, None, True, trace, 'occupancy_coarse')
+        z_fine, w = ray_utils.importance_z_from_raw(raw, z, d, importance_samples_per_ray, want_weights=trace is not None)
+        _note(trace, coarse_z=z, coarse_w=w)
+        return z_fine, None
     if fine_net is None:
         return z, (None if TERMINATION_EPS > 0 else coarse_net.forward_rays(o, d, z, precision=precision, role='shading'))
     # with a fine net the coarse pass only places the importance samples (only its density is used, render_utils.py:139-141: the
@@ -315,7 +345,9 @@ def bkg_place_z(coarse_net, fine_net, o, d, near, far, samples_per_ray, importan
 
 def bkg_shade(net, o, d, z, precision=None, trace=None, occluder=None, dz=None):
     """The background pass that is composited, on its final samples (render_utils.py:148-151, 294-297): whole, or -- TERMINATION_EPS > 0 --
-    marched front to back at eps (`occluder`, `dz`: march_pass_rays)"""
+    marched front to back at eps (`occluder`, `dz`: march_pass_rays), or -- a grid attached (occupancy.attach) -- on its occupied samples"""
+    if _occupancy_on(net):
+        return _occupancy_pass(net, o, d, z, precision, 'shading', False, trace, 'occupancy')
     if TERMINATION_EPS > 0:
         stats = {} if trace is not None else None
         raw = march_pass_rays(net, o, d, z, TERMINATION_EPS, precision=precision, stats=stats, occluder=occluder, dz=dz)
@@ -471,7 +503,7 @@ def render_hybrid_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far,
     intervals bound the merged transmittance from above; behind the body the background sees its own x the body's): a pixel moves
     by < 2 eps, for bodies of any opacity (tests/test_hip_march.py: opaque and semi-transparent).
     The plain case (no trace, no replay, no termination) is ONE C call per batch: render_hybrid_rays_fused, bit-identical."""
-    if TERMINATION_EPS <= 0 and trace is None and given is None:
+    if TERMINATION_EPS <= 0 and trace is None and given is None and not _occupancy_on(coarse_bkg, fine_bkg):
         return render_hybrid_rays_fused(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far, posed_verts, mesh, samples_per_ray,
                                         importance_samples_per_ray, white_bkg, geo_threshold, precision)
     R = o.shape[0]
