@@ -286,6 +286,26 @@ int nm_mlp_forward_samples(nm_mlp_t mlp, const float* origin, const float* direc
 int nm_mlp_sigma_samples(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S,
                          const int32_t* sample_idx, const int32_t* n_dev, int64_t n_max, int precision, float sigma_scale, float* out,
                          nm_stream_t stream);
+/* ---------------------------------------------------------------------------------------------
+ * K11b  occupancy-grid empty-space skipping for the human passes -- reference utils/render_utils.py:213-229, 320-329 (every sample).
+ * Same grid, box and skipped-sample convention as K11 above; a human net's grid lives in CANONICAL space.
+ *
+ * nm_occ_compact_points: point_idx [n] receives the ascending indices k of the points pts [n,3] whose cell is occupied or that lie
+ *   outside the box; counts[0] = their number, counts[1] = the skipped (device int32[2]).  The cell test and the scan of
+ *   nm_occ_compact_samples.  workspace: nm_occ_compact_workspace_ints(n) int32.
+ * nm_mlp_forward_listed: nm_mlp_forward on the listed points only (in_mode 4): launch entry i evaluates point k = point_idx[i] (pts[k],
+ *   dirs[k]) and writes out[k] [n_points,4]; the first *n_dev entries (n_dev nullable: n_max) are evaluated, nothing else of out is
+ *   touched.  Bit-identical to the matching rows of nm_mlp_forward.  NM_PREC_FP32 is not available in this form.
+ * nm_render_rays_human_occ: nm_render_rays_human with the grid (bits, res, aabb).  raw_out [R,S,4] is zeroed, then: mesh == NULL
+ *   (canonical render) -> nm_occ_compact_samples on o + d z and nm_mlp_forward_samples; else sample -> nm_warp_to_canonical ->
+ *   nm_occ_compact_points on the canonical points -> nm_mlp_forward_listed.  counts (device int32[2]) = (evaluated, skipped)
+ *   samples.  workspace: nm_render_rays_human_occ_workspace_floats(R, S, posed) floats; it begins with nm_render_rays_human's layout.
+ *   No host synchronisation, no allocation.  (Declared with the fused passes below.)
+ * ------------------------------------------------------------------------------------------- */
+int nm_occ_compact_points(const uint32_t* bits, int res, const float* aabb, const float* pts, int64_t n, int32_t* point_idx, int32_t* counts,
+                          int32_t* workspace, nm_stream_t stream);
+int nm_mlp_forward_listed(nm_mlp_t mlp, const float* pts, const float* dirs, int64_t n_points, const int32_t* point_idx, const int32_t* n_dev,
+                          int64_t n_max, int precision, float sigma_scale, float* out, nm_stream_t stream);
 /* T[r] *= prod_{i in chunk} (1 - alpha_i + 1e-10) for the listed rays (ray_idx nullable = rays 0..n_rays-1): the
  * transmittance factors of raw2outputs (render_utils.py:85-95) over samples s0 .. s0+S-1 of raw [R,S_total,4]; rays whose T
  * falls below the caller's epsilon are dropped by nm_compact_hits(eps, T). */
@@ -431,6 +451,12 @@ int64_t nm_render_rays_human_workspace_floats(int64_t R, int S, int posed);
 int nm_render_rays_human(nm_mlp_t human, nm_mesh_t mesh, const double* T, const float* origin, const float* direction, const float* near,
                          const float* far, int64_t R, int S, const float* t_vals, int white_bkg, float sigma_scale, int precision,
                          float* workspace, float* raw_out, float* z_out, float* rgb, float* depth, float* acc, nm_stream_t stream);
+/* K11b: nm_render_rays_human with an occupancy grid -- see the K11b block above */
+int64_t nm_render_rays_human_occ_workspace_floats(int64_t R, int S, int posed);
+int nm_render_rays_human_occ(nm_mlp_t human, nm_mesh_t mesh, const double* T, const uint32_t* bits, int res, const float* aabb, const float* origin,
+                             const float* direction, const float* near, const float* far, int64_t R, int S, const float* t_vals, int white_bkg,
+                             float sigma_scale, int precision, float* workspace, float* raw_out, float* z_out, int32_t* counts, float* rgb, float* depth,
+                             float* acc, nm_stream_t stream);
 /* render_hybrid_nerf's per-batch body (utils/render_utils.py:287-353; SURVEY 8b nm_render_rays_hybrid) as one call: two-pass background
  * of every ray (scalar bkg_near / bkg_far) and its composite, near / far against the posed body `verts` [V,3] (geo_threshold), compaction
  * of the hit rays (ONE host read: their count), human pass of the hit rays through `mesh` / `T`, merged composite and the human-only

@@ -14,6 +14,9 @@ int check_hip(hipError_t e, const char* what);
 constexpr int kWave = 64;  // CDNA wavefront width
 
 inline hipStream_t as_stream(nm_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+// the net was created with the plain head (use_viewdirs=False): its whole-network output is (r, g, b, sigma) without a density-only form
+// at NM_PREC_I8X3 (mlp_host.hip)
+bool mlp_plain_head(nm_mlp_t mlp);
 
 }  // namespace nm
 

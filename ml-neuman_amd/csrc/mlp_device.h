@@ -63,10 +63,12 @@ struct MlpArgs {
     int64_t n;
     int S;
     int in_mode;             // 0: points / directions given; 1: rays + z [R,S]; 2: a chunk of S samples starting at s0 of the listed rays;
-                             // 3: the listed samples of rays + z [R,S] (flat indices r * S + s, occupancy.hip nm_occ_compact_samples)
-    const int* ray_idx;      // in_mode 2: [n / S] global ray numbers (compacted list of live rays); in_mode 3: [n] flat sample indices
+                             // 3: the listed samples of rays + z [R,S] (flat indices r * S + s, occupancy.hip nm_occ_compact_samples);
+                             // 4: the listed points of pts / dirs [*,3] (indices k, occupancy.hip nm_occ_compact_points), record out[k]
+    const int* ray_idx;      // in_mode 2: [n / S] global ray numbers (compacted list of live rays); in_mode 3: [n] flat sample indices;
+                             // in_mode 4: [n] point indices
     const int* n_rays_dev;   // in_mode 2: the list's length lives on the device (no host sync between chunks); n = *n_rays_dev * S;
-                             // in_mode 3: n = *n_rays_dev
+                             // in_mode 3 / 4: n = *n_rays_dev
     int s0, S_total;         // in_mode 2: z and out are [R, S_total] (x4); this launch covers samples s0 .. s0 + S - 1
     int stop_stage;          // -2 = run everything
     float sigma_scale;
@@ -113,13 +115,14 @@ __device__ __forceinline__ float pe_feature(int p, float x0, float x1, float x2,
 
 // sample i of the launch -> the 3-vector to encode (position or direction) and, for the stores, its record in `out`
 __device__ __forceinline__ int64_t sample_record(const MlpArgs& a, int64_t i) {
-    if (a.in_mode == 3) return a.ray_idx[i];                   // out[r, s] of the listed sample itself
+    if (a.in_mode >= 3) return a.ray_idx[i];                   // out[r, s] / out[k] of the listed sample / point itself
     if (a.in_mode != 2) return i;
     const int64_t j = i / a.S;
     return (int64_t)a.ray_idx[j] * a.S_total + a.s0 + (i - j * a.S);
 }
 __device__ __forceinline__ void sample_input(const MlpArgs& a, int64_t i, bool is_dir, float& x0, float& x1, float& x2) {
-    if (a.in_mode == 0) {
+    if (a.in_mode == 0 || a.in_mode == 4) {
+        if (a.in_mode == 4) i = a.ray_idx[i];                   // the listed point k: then exactly in_mode 0's input
         const float* src = (is_dir ? a.dirs : a.pts) + i * 3;
         x0 = src[0]; x1 = src[1]; x2 = src[2];
         return;
@@ -476,10 +479,10 @@ __device__ __forceinline__ void dump_act(const uint4* lds, bool from_pe, int wid
 
 // PROF: accumulate s_memtime deltas per wave into 6 buckets {pe, k-loops, wait before epilogue, epilogue, wait after
 // epilogue, tail} (a.prof[(block*8 + wave)*8 + bucket]); a separate instantiation so the production kernel is untouched.
-// in_mode 2 / 3 launches size themselves on the device: the live-ray (sample) count is the output of the compaction that ran just before
+// in_mode 2 / 3 / 4 launches size themselves on the device: the live-ray (sample) count is the output of the compaction that ran just before
 __device__ __forceinline__ MlpArgs resolve_args(MlpArgs a) {
     if (a.in_mode == 2 && a.n_rays_dev) a.n = (int64_t)(*a.n_rays_dev) * a.S;
-    if (a.in_mode == 3 && a.n_rays_dev) a.n = *a.n_rays_dev;
+    if (a.in_mode >= 3 && a.n_rays_dev) a.n = *a.n_rays_dev;
     return a;
 }
 

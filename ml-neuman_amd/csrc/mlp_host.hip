@@ -964,6 +964,23 @@ int nm_mlp_sigma_samples(nm_mlp_t mlp, const float* origin, const float* directi
     return forward_samples("nm_mlp_sigma_samples", 1, mlp, origin, direction, z_vals, R, S, sample_idx, n_dev, n_max, precision, sigma_scale, out, stream);
 }
 
+}  // extern "C"
+
+bool nm::mlp_plain_head(nm_mlp_t m) { return m && m->desc.plain_head; }
+
+extern "C" {
+
+int nm_mlp_forward_listed(nm_mlp_t mlp, const float* pts, const float* dirs, int64_t n_points, const int32_t* point_idx, const int32_t* n_dev,
+                          int64_t n_max, int precision, float sigma_scale, float* out, nm_stream_t stream) {
+    NM_REQUIRE(n_max == 0 || (pts && dirs && point_idx && out), "nm_mlp_forward_listed: null pointer");
+    NM_REQUIRE(n_points >= 0 && n_max >= 0 && n_max <= n_points && n_points < (1ll << 31), "nm_mlp_forward_listed: bad sizes (n_points=%lld n_max=%lld)",
+               (long long)n_points, (long long)n_max);
+    NM_REQUIRE(precision != NM_PREC_FP32, "nm_mlp_forward_listed: the exact-f32 validation kernel has no point-list form");
+    NM_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "nm_mlp_forward_listed: out must be 16-byte aligned");
+    nm::MlpChunk c{point_idx, n_dev, 0, 1};
+    return mlp_dispatch(mlp, pts, dirs, nullptr, nullptr, nullptr, n_max, 1, 4, precision, -2, sigma_scale, out, nullptr, stream, nullptr, 0, &c);
+}
+
 int nm_mlp_forward_profile(nm_mlp_t mlp, const float* pts, const float* dirs, int64_t n, int precision, float* out,
                            uint64_t* cycles, nm_stream_t stream) {
     NM_REQUIRE(n == 0 || (pts && dirs && out && cycles), "nm_mlp_forward_profile: null pointer");

@@ -1,4 +1,4 @@
-// K11: occupancy grid for empty-space skipping in the background passes (reference utils/render_utils.py:131-151, 287-297 evaluate
+// K11 / K11b: occupancy grid for empty-space skipping in the background and human passes (reference utils/render_utils.py:131-151, 287-297 evaluate
 // every sample; a sample skipped here keeps raw = 0, which raw2outputs turns into alpha = 0 and weight 0 -- exactly what a sample with
 // relu(sigma) = 0 gets, so on every ray whose skipped samples all have relu(sigma) = 0 the frame is unchanged bit for bit).
 //
@@ -7,7 +7,10 @@
 //     cell row laid out as one ray along +x per probe; thresholded, dilated by `dilate` cells (a (2 dilate + 1)^3 max) and packed.
 //   * nm_occ_compact_samples: the flat indices r * S + s of the samples of R x S rays whose cell is occupied (or that lie outside the
 //     box), ascending, and their count -- both on the device: wave ballot + popcount prefix, a two-level scan (nearfar.hip's scheme, K2b).
-//   * nm_mlp_forward_samples / nm_mlp_sigma_samples (mlp_host.hip, in_mode 3 of mlp_device.h) evaluate the listed samples only.
+//   * nm_occ_compact_points (K11b): the same for the points of an [n,3] array -- the warped canonical points of a posed human pass; the
+//     same cell test and scan, only the point source differs.
+//   * nm_mlp_forward_samples / nm_mlp_sigma_samples (mlp_host.hip, in_mode 3 of mlp_device.h) evaluate the listed samples only,
+//     nm_mlp_forward_listed (in_mode 4) the listed points.
 //
 // Cell (i, j, k) along (x, y, z) is bit c = (k * res + j) * res + i, word c >> 5, bit c & 31.  Every buffer is the caller's.
 #include <cmath>
@@ -111,32 +114,61 @@ __global__ __launch_bounds__(256) void occ_pack_kernel(const float* __restrict__
     bits[w] = word;
 }
 
-// sample i = r * S + s: its point exactly as mlp_device.h sample_input builds it (o + d * z, two roundings: -ffp-contract=off), then its cell
-__device__ __forceinline__ bool sample_occupied(const OccBox& B, const uint32_t* __restrict__ bits, const float* __restrict__ origin,
-                                                const float* __restrict__ direction, const float* __restrict__ z, int64_t i, int S) {
-    const int64_t r = i / S;
-    const float zz = z[i];
-    const float* o = origin + r * 3;
-    const float* d = direction + r * 3;
-    const float p[3] = {o[0] + d[0] * zz, o[1] + d[1] * zz, o[2] + d[2] * zz};
+// the cell test: occupied, or outside the box (or NaN) -- conservatively occupied
+__device__ __forceinline__ bool point_occupied(const OccBox& B, const uint32_t* __restrict__ bits, const float (&p)[3]) {
     int c[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float t = (p[a] - B.lo[a]) * B.inv[a];
-        if (!(t >= 0.f && t < (float)B.res)) return true;          // outside the box (or NaN): conservatively occupied
+        if (!(t >= 0.f && t < (float)B.res)) return true;
         c[a] = min((int)t, B.res - 1);
     }
     const int64_t cell = ((int64_t)c[2] * B.res + c[1]) * B.res + c[0];
     return (bits[cell >> 5] >> (cell & 31)) & 1u;
 }
 
-// pass 1: occupied samples per block
-__global__ __launch_bounds__(kOccBlock) void occ_count_kernel(const OccBox B, const uint32_t* __restrict__ bits, const float* __restrict__ origin,
-                                                              const float* __restrict__ direction, const float* __restrict__ z, int64_t n, int S,
+// the points the compaction lists: sample i = r * S + s of rays + z, built exactly as mlp_device.h sample_input builds it (o + d * z,
+// two roundings: -ffp-contract=off) ...
+struct SamplePoints {
+    const float* origin;
+    const float* direction;
+    const float* z;
+    int S;
+    __device__ __forceinline__ void point(int64_t i, float (&p)[3]) const {
+        const int64_t r = i / S;
+        const float zz = z[i];
+        const float* o = origin + r * 3;
+        const float* d = direction + r * 3;
+        p[0] = o[0] + d[0] * zz;
+        p[1] = o[1] + d[1] * zz;
+        p[2] = o[2] + d[2] * zz;
+    }
+};
+// ... or point i of an [n,3] array (the warped canonical points of a posed human pass)
+struct GivenPoints {
+    const float* pts;
+    __device__ __forceinline__ void point(int64_t i, float (&p)[3]) const {
+        p[0] = pts[i * 3];
+        p[1] = pts[i * 3 + 1];
+        p[2] = pts[i * 3 + 2];
+    }
+};
+
+template <class Src>
+__device__ __forceinline__ bool listed(const OccBox& B, const uint32_t* __restrict__ bits, const Src& src, int64_t i, int64_t n) {
+    if (i >= n) return false;
+    float p[3];
+    src.point(i, p);
+    return point_occupied(B, bits, p);
+}
+
+// pass 1: occupied points per block
+template <class Src>
+__global__ __launch_bounds__(kOccBlock) void occ_count_kernel(const OccBox B, const uint32_t* __restrict__ bits, const Src src, int64_t n,
                                                               int32_t* __restrict__ block_counts) {
     __shared__ int wave_cnt[kOccBlock / 64];
     const int64_t i = blockIdx.x * (int64_t)kOccBlock + threadIdx.x;
-    const bool occ = i < n && sample_occupied(B, bits, origin, direction, z, i, S);
+    const bool occ = listed(B, bits, src, i, n);
     const unsigned long long b = __ballot(occ);
     if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = __popcll(b);
     __syncthreads();
@@ -179,14 +211,14 @@ __global__ __launch_bounds__(1024) void occ_scan_kernel(int32_t* __restrict__ bl
     }
 }
 
-// pass 3: the occupied samples' flat indices, ascending
-__global__ __launch_bounds__(kOccBlock) void occ_write_kernel(const OccBox B, const uint32_t* __restrict__ bits, const float* __restrict__ origin,
-                                                              const float* __restrict__ direction, const float* __restrict__ z, int64_t n, int S,
+// pass 3: the occupied points' indices, ascending
+template <class Src>
+__global__ __launch_bounds__(kOccBlock) void occ_write_kernel(const OccBox B, const uint32_t* __restrict__ bits, const Src src, int64_t n,
                                                               const int32_t* __restrict__ block_offsets, int32_t* __restrict__ idx) {
     __shared__ int wave_cnt[kOccBlock / 64];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int64_t i = blockIdx.x * (int64_t)kOccBlock + threadIdx.x;
-    const bool occ = i < n && sample_occupied(B, bits, origin, direction, z, i, S);
+    const bool occ = listed(B, bits, src, i, n);
     const unsigned long long b = __ballot(occ);
     if (lane == 0) wave_cnt[wid] = __popcll(b);
     __syncthreads();
@@ -199,6 +231,31 @@ bool box_ok(const float* aabb) {
     for (int a = 0; a < 3; ++a)
         if (!(aabb[a] < aabb[3 + a]) || !std::isfinite(aabb[a]) || !std::isfinite(aabb[3 + a])) return false;
     return true;
+}
+
+// the three passes: count per block, scan (counts = (kept, skipped)), write -- the count stays on the device
+template <class Src>
+int occ_compact(const char* what, const uint32_t* bits, int res, const float* aabb, const Src& src, int64_t n, int32_t* idx, int32_t* counts,
+                int32_t* workspace, hipStream_t st) {
+    OccBox B;
+    for (int a = 0; a < 3; ++a) {
+        B.lo[a] = aabb[a];
+        B.inv[a] = (float)res / (aabb[3 + a] - aabb[a]);
+    }
+    B.res = res;
+    const int nblocks = (int)((n + kOccBlock - 1) / kOccBlock);
+    if (nblocks > 0) {
+        hipLaunchKernelGGL(occ_count_kernel<Src>, dim3(nblocks), dim3(kOccBlock), 0, st, B, bits, src, n, workspace);
+        if (int e = nm::check_launch("occ_count_kernel")) return e;
+    }
+    hipLaunchKernelGGL(occ_scan_kernel, dim3(1), dim3(1024), 0, st, workspace, nblocks, n, counts);
+    if (int e = nm::check_launch("occ_scan_kernel")) return e;
+    if (nblocks > 0) {
+        hipLaunchKernelGGL(occ_write_kernel<Src>, dim3(nblocks), dim3(kOccBlock), 0, st, B, bits, src, n, workspace, idx);
+        if (int e = nm::check_launch("occ_write_kernel")) return e;
+    }
+    (void)what;
+    return NM_OK;
 }
 
 }  // namespace
@@ -244,6 +301,9 @@ int nm_occ_build(nm_mlp_t mlp, const float* aabb, int res, int probes, int dilat
         for (int a = 0; a < 3; ++a) P.off[k][a] = nm_occ_probe_offset(probes, seed, k, a);
     P.res = res;
     P.probes = probes;
+    // the plain-head net (use_viewdirs=False: a human net without specular_can) has no density-only form at NM_PREC_I8X3: its whole-network
+    // launch gives the same sigma
+    const bool whole = precision == NM_PREC_I8X3 && nm::mlp_plain_head(mlp);
     const int64_t n_rows = (int64_t)res * res;
     int64_t batch = kBuildOutFloats / ((int64_t)probes * res * 4);
     if (batch < 1) batch = 1;
@@ -258,7 +318,8 @@ int nm_occ_build(nm_mlp_t mlp, const float* aabb, int res, int probes, int dilat
         const int64_t rays = nr * probes;
         hipLaunchKernelGGL(occ_probe_rays_kernel, dim3((unsigned)((rays * res + 255) / 256)), dim3(256), 0, st, P, row0, rays, origin, direction, z);
         if (int e = nm::check_launch("occ_probe_rays_kernel")) return e;
-        if (int e = nm_mlp_sigma_rays(mlp, origin, direction, z, rays, res, precision, 1.f, raw, stream)) return e;
+        if (int e = whole ? nm_mlp_forward_rays(mlp, origin, direction, z, rays, res, precision, 1.f, raw, stream)
+                          : nm_mlp_sigma_rays(mlp, origin, direction, z, rays, res, precision, 1.f, raw, stream)) return e;
         hipLaunchKernelGGL(occ_cell_max_kernel, dim3((unsigned)((nr * res + 255) / 256)), dim3(256), 0, st, reinterpret_cast<const float4*>(raw), row0,
                            nr, res, probes, maxsig);
         if (int e = nm::check_launch("occ_cell_max_kernel")) return e;
@@ -277,26 +338,18 @@ int nm_occ_compact_samples(const uint32_t* bits, int res, const float* aabb, con
     NM_REQUIRE(res >= 4 && res <= 256 && res % 4 == 0, "nm_occ_compact_samples: res %d outside 4..256 or not a multiple of 4", res);
     NM_REQUIRE(R >= 0 && S >= 1 && R * (int64_t)S < (1ll << 31), "nm_occ_compact_samples: bad sizes (R=%lld S=%d)", (long long)R, S);
     NM_REQUIRE(box_ok(aabb), "nm_occ_compact_samples: the box must have finite lo < hi on every axis");
-    hipStream_t st = nm::as_stream(stream);
-    OccBox B;
-    for (int a = 0; a < 3; ++a) {
-        B.lo[a] = aabb[a];
-        B.inv[a] = (float)res / (aabb[3 + a] - aabb[a]);
-    }
-    B.res = res;
-    const int64_t n = R * (int64_t)S;
-    const int nblocks = (int)((n + kOccBlock - 1) / kOccBlock);
-    if (nblocks > 0) {
-        hipLaunchKernelGGL(occ_count_kernel, dim3(nblocks), dim3(kOccBlock), 0, st, B, bits, origin, direction, z_vals, n, S, workspace);
-        if (int e = nm::check_launch("occ_count_kernel")) return e;
-    }
-    hipLaunchKernelGGL(occ_scan_kernel, dim3(1), dim3(1024), 0, st, workspace, nblocks, n, counts);
-    if (int e = nm::check_launch("occ_scan_kernel")) return e;
-    if (nblocks > 0) {
-        hipLaunchKernelGGL(occ_write_kernel, dim3(nblocks), dim3(kOccBlock), 0, st, B, bits, origin, direction, z_vals, n, S, workspace, sample_idx);
-        if (int e = nm::check_launch("occ_write_kernel")) return e;
-    }
-    return NM_OK;
+    return occ_compact("nm_occ_compact_samples", bits, res, aabb, SamplePoints{origin, direction, z_vals, S}, R * (int64_t)S, sample_idx, counts, workspace,
+                       nm::as_stream(stream));
+}
+
+int nm_occ_compact_points(const uint32_t* bits, int res, const float* aabb, const float* pts, int64_t n, int32_t* point_idx, int32_t* counts,
+                          int32_t* workspace, nm_stream_t stream) {
+    NM_REQUIRE(bits && aabb && counts && workspace, "nm_occ_compact_points: null pointer");
+    NM_REQUIRE(n == 0 || (pts && point_idx), "nm_occ_compact_points: null pointer");
+    NM_REQUIRE(res >= 4 && res <= 256 && res % 4 == 0, "nm_occ_compact_points: res %d outside 4..256 or not a multiple of 4", res);
+    NM_REQUIRE(n >= 0 && n < (1ll << 31), "nm_occ_compact_points: bad size (n=%lld)", (long long)n);
+    NM_REQUIRE(box_ok(aabb), "nm_occ_compact_points: the box must have finite lo < hi on every axis");
+    return occ_compact("nm_occ_compact_points", bits, res, aabb, GivenPoints{pts}, n, point_idx, counts, workspace, nm::as_stream(stream));
 }
 
 }  // extern "C"

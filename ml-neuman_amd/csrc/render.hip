@@ -78,6 +78,49 @@ int nm_render_rays_human(nm_mlp_t human, nm_mesh_t mesh, const double* T, const 
     return NM_OK;
 }
 
+// K11b: the human pass with occupancy-grid empty-space skipping (occupancy.hip).  The workspace starts with nm_render_rays_human's layout
+// (posed: points | canonical points | canonical directions; disp), then the kept list and the compaction's scratch.
+int64_t nm_render_rays_human_occ_workspace_floats(int64_t R, int S, int posed) {
+    return nm_render_rays_human_workspace_floats(R, S, posed) + align4(R * S) + align4(nm_occ_compact_workspace_ints(R * S));
+}
+
+int nm_render_rays_human_occ(nm_mlp_t human, nm_mesh_t mesh, const double* T, const uint32_t* bits, int res, const float* aabb, const float* origin,
+                             const float* direction, const float* near, const float* far, int64_t R, int S, const float* t_vals, int white_bkg,
+                             float sigma_scale, int precision, float* workspace, float* raw_out, float* z_out, int32_t* counts, float* rgb, float* depth,
+                             float* acc, nm_stream_t stream) {
+    NM_REQUIRE(bits && aabb && counts, "nm_render_rays_human_occ: null pointer");
+    NM_REQUIRE(R == 0 || (human && origin && direction && near && far && t_vals && workspace && raw_out && z_out), "nm_render_rays_human_occ: null pointer");
+    NM_REQUIRE(R >= 0 && S >= 1 && (mesh == nullptr) == (T == nullptr), "nm_render_rays_human_occ: a posed mesh and its transforms go together");
+    NM_REQUIRE(R * (int64_t)S < (1ll << 31), "nm_render_rays_human_occ: too many samples (R=%lld S=%d)", (long long)R, S);
+    hipStream_t st = nm::as_stream(stream);
+    int rc;
+    if (R == 0) return nm::check_hip(hipMemsetAsync(counts, 0, 8, st), "nm_render_rays_human_occ: counts");
+    // a skipped sample keeps raw = 0: alpha 0, weight 0 -- what relu(sigma) = 0 gives
+    if ((rc = nm::check_hip(hipMemsetAsync(raw_out, 0, (size_t)(R * S) * 16, st), "nm_render_rays_human_occ: raw"))) return rc;
+    const int64_t base = nm_render_rays_human_workspace_floats(R, S, mesh != nullptr);
+    float* disp = workspace + (mesh ? 3 * align4(R * S * 3) : 0);
+    int32_t* idx = reinterpret_cast<int32_t*>(workspace + base);
+    int32_t* cws = idx + align4(R * S);
+    if (!mesh) {                                                  // canonical: the grid is tested on o + d z itself (in_mode 3)
+        if ((rc = nm_ray_to_samples(origin, direction, near, far, R, S, t_vals, 0, nullptr, nullptr, nullptr, z_out, stream))) return rc;
+        if ((rc = nm_occ_compact_samples(bits, res, aabb, origin, direction, z_out, R, S, idx, counts, cws, stream))) return rc;
+        if ((rc = nm_mlp_forward_samples(human, origin, direction, z_out, R, S, idx, counts, R * S, precision, sigma_scale, raw_out, stream))) return rc;
+    } else {                                                      // posed: the grid lives in canonical space -- tested on the WARPED points (in_mode 4)
+        float* pts = workspace;
+        float* can_pts = pts + align4(R * S * 3);
+        float* can_dirs = can_pts + align4(R * S * 3);
+        if ((rc = nm_ray_to_samples(origin, direction, near, far, R, S, t_vals, 0, nullptr, pts, nullptr, z_out, stream))) return rc;
+        if ((rc = nm_warp_to_canonical(mesh, pts, R, S, T, can_pts, can_dirs, nullptr, stream))) return rc;
+        if ((rc = nm_occ_compact_points(bits, res, aabb, can_pts, R * S, idx, counts, cws, stream))) return rc;
+        if ((rc = nm_mlp_forward_listed(human, can_pts, can_dirs, R * S, idx, counts, R * S, precision, sigma_scale, raw_out, stream))) return rc;
+    }
+    if (rgb) {
+        NM_REQUIRE(depth && acc, "nm_render_rays_human_occ: rgb, depth and acc go together");
+        if ((rc = nm_composite(raw_out, z_out, direction, R, S, white_bkg, nullptr, rgb, disp, acc, nullptr, depth, stream))) return rc;
+    }
+    return NM_OK;
+}
+
 // (the merged list lives in LDS now: nothing is needed; kept for callers that size a workspace)
 int64_t nm_merge_composite_workspace_floats(int64_t R, int Sa, int Sb) { (void)R; (void)Sa; (void)Sb; return 4; }
 

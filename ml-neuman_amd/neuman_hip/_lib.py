@@ -47,6 +47,11 @@ SIGNATURES = {
     "nm_occ_compact_samples": (i32, [c_i32p, i32, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, c_i32p, c_i32p, c_i32p, c_stream]),
     "nm_mlp_forward_samples": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, c_i32p, c_i32p, i64, i32, ctypes.c_float, c_f32p, c_stream]),
     "nm_mlp_sigma_samples": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, c_i32p, c_i32p, i64, i32, ctypes.c_float, c_f32p, c_stream]),
+    "nm_occ_compact_points": (i32, [c_i32p, i32, ctypes.c_void_p, c_f32p, i64, c_i32p, c_i32p, c_i32p, c_stream]),
+    "nm_mlp_forward_listed": (i32, [ctypes.c_void_p, c_f32p, c_f32p, i64, c_i32p, c_i32p, i64, i32, ctypes.c_float, c_f32p, c_stream]),
+    "nm_render_rays_human_occ_workspace_floats": (i64, [i64, i32, i32]),
+    "nm_render_rays_human_occ": (i32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32p, i32, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, i64, i32,
+                                       c_f32p, i32, ctypes.c_float, i32, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "nm_compact_hits": (i32, [c_f32p, c_f32p, i64, c_i32p, c_i32p, c_i32p, c_i32p, c_stream]),
     "nm_mlp_pack_bytes": (i64, [ctypes.POINTER(MlpDesc)]),
     "nm_mlp_pack_i8s_bytes": (i64, [ctypes.POINTER(MlpDesc)]),

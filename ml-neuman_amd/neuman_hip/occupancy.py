@@ -1,4 +1,4 @@
-"""Occupancy-grid empty-space skipping for the background passes (csrc/occupancy.hip).
+"""Occupancy-grid empty-space skipping for the background and human passes (csrc/occupancy.hip).
 
 The reference evaluates every sample of every ray (utils/render_utils.py:131-151, 287-297).  A net with a grid attached
 (`attach`) has its background passes -- render_utils.bkg_place_z / bkg_shade, i.e. render_vanilla, render_hybrid_nerf,
@@ -10,6 +10,19 @@ attached nothing changes.
 
     grid = OccupancyGrid.from_net(coarse, aabb=((-2, -2, -4), (2, 2, 0)))
     attach(coarse, grid); attach(fine, OccupancyGrid.from_net(fine, aabb=...))
+
+Human nets (K11b).  A grid attached to a human net (HumanNeRF.coarse_human_net, either head) lives in CANONICAL space and serves
+every human pass -- render_utils.human_pass_rays (nm_render_rays_human_occ), so render_smpl_nerf (canonical and posed) and the human
+legs of render_hybrid_nerf / render_hybrid_nerf_multi_persons (one grid per actor's net), and human_march_rays (early termination).
+The canonical render tests the grid on o + d z; the posed pass on the WARPED canonical points (nm_warp_to_canonical, then
+nm_occ_compact_points).  The fused hybrid call gives way to the unfused passes while any grid is attached.
+
+    grid = OccupancyGrid.from_net(human.coarse_human_net, canonical_aabb(static_verts, 0.1))
+    attach(human.coarse_human_net, grid)
+
+Training never consults a grid: the trainers evaluate their nets through the training forward (Joiner.forward in train() mode,
+neuman_hip/train.py) on the points of the batch, which knows nothing of grids -- a human-trainer step is the same with or without
+one (tests/test_hip_occupancy_human.py).  Rebuild the grid (from_net) after training has moved the density.
 
 Cells: `res`^3 over the box, cell (i, j, k) along (x, y, z); masks are boolean tensors indexed [i, j, k].
 """
@@ -58,6 +71,19 @@ def rays_aabb(o, d, near, far, pad=1e-3):
     lo, hi = ends.min(0).values.cpu(), ends.max(0).values.cpu()
     g = (hi - lo).clamp_min(1e-6) * pad
     return torch.cat([lo - g, hi + g])
+
+
+def canonical_aabb(static_verts, margin=0.1):
+    """The box of a human net's grid: the canonical body's vertices (e.g. the static / da-pose SMPL vertices, [V,3]) grown by `margin`
+    scene units per side -> (lo xyz, hi xyz) float32 on the host.  The body's density lives near its surface; what lies outside the
+    box is always evaluated (conservatively occupied)."""
+    v = torch.as_tensor(static_verts).reshape(-1, 3).to(torch.float32).cpu()
+    if v.shape[0] == 0 or not bool(torch.isfinite(v).all()):
+        raise ValueError("canonical_aabb: static_verts must be a non-empty finite [V,3] array")
+    m = float(margin)
+    if not m >= 0.0:
+        raise ValueError(f"canonical_aabb: margin must be >= 0, got {margin}")
+    return _check_box(torch.cat([v.min(0).values - m, v.max(0).values + m]))
 
 
 class OccupancyGrid:
@@ -134,6 +160,29 @@ class OccupancyGrid:
         return cls(sd['aabb'], int(sd['res']), bits, sd.get('meta'))
 
     # ---- the sample list of a pass ----------------------------------------------------------
+    def box_c(self):
+        return (ctypes.c_float * 6)(*self.aabb.tolist())
+
+    def check_device(self, dev):
+        if self.bits.device != dev:
+            raise _lib.NeumanHipError(f"the grid lives on {self.bits.device}, the rays on {dev}: attach() the grid to the net on its device")
+
+    def compact_points(self, pts):
+        """-> (point_idx int32 [n]: indices of the points pts [n,3] to evaluate, ascending, the first counts[0] live; counts int32 [2] =
+        (evaluated, skipped)), both on the device (nm_occ_compact_points)"""
+        pts = pts.reshape(-1, 3).contiguous()
+        n = pts.shape[0]
+        dev = pts.device
+        self.check_device(dev)
+        idx = torch.empty(n, device=dev, dtype=torch.int32)
+        counts = torch.zeros(2, device=dev, dtype=torch.int32)
+        L = _lib.lib()
+        ws = torch.empty(int(L.nm_occ_compact_workspace_ints(n)), device=dev, dtype=torch.int32)
+        _lib.check(L.nm_occ_compact_points(_lib.dev_ptr(self.bits, torch.int32), self.res, self.box_c(), _lib.dev_ptr(pts, name='pts'), n,
+                                           _lib.dev_ptr(idx, torch.int32), _lib.dev_ptr(counts, torch.int32), _lib.dev_ptr(ws, torch.int32),
+                                           _lib.stream_ptr()), "nm_occ_compact_points")
+        return idx, counts
+
     def compact(self, o, d, z):
         """-> (sample_idx int32 [R*S]: flat indices r*S + s of the samples to evaluate, ascending, the first counts[0] live;
         counts int32 [2] = (evaluated, skipped)), both on the device"""
@@ -153,8 +202,9 @@ class OccupancyGrid:
 
 
 def attach(net, grid):
-    """Give `net` (a background Joiner) an occupancy grid: its background passes skip the grid's empty cells from now on.
-    Coarse and fine nets have different densities: each gets its own grid (the same object may serve a net used for both)."""
+    """Give `net` (a background Joiner, or a human net: a grid in canonical space) an occupancy grid: its render passes skip the grid's
+    empty cells from now on.  Coarse and fine nets have different densities: each gets its own grid (the same object may serve a net used
+    for both); so does each actor's human net."""
     _refuse_time_net(net)
     if not isinstance(grid, OccupancyGrid):
         raise TypeError(f"attach() takes an OccupancyGrid, got {type(grid).__name__}")
@@ -194,3 +244,25 @@ def forward_rays(net, o, d, z, precision=None, role=None, sigma_only=False, stat
         stats['evaluated'] = stats.get('evaluated', 0) + int(counts[0].item())
         stats['total'] = stats.get('total', 0) + R * S
     return raw
+
+
+def forward_points(net, pts, dirs, precision=None, sigma_scale=1.0, role=None, stats=None):
+    """net(pts, dirs) on the points its grid keeps only (nm_occ_compact_points + nm_mlp_forward_listed): [..., 4], zero on every skipped
+    point.  `stats` (a dict) receives 'evaluated' / 'total' point counts (one host read)."""
+    grid = grid_of(net)
+    net._guard(pts, dirs)
+    shp = pts.shape[:-1]
+    p = pts.reshape(-1, 3).contiguous()
+    d = dirs.reshape(-1, 3).contiguous()
+    n = p.shape[0]
+    out = torch.zeros((n, 4), device=p.device, dtype=torch.float32)
+    if n == 0:
+        return out.reshape(*shp, 4)
+    idx, counts = grid.compact_points(p)
+    _lib.check(_lib.lib().nm_mlp_forward_listed(net.handle(), _lib.dev_ptr(p, name='pts'), _lib.dev_ptr(d, name='dirs'), n, _lib.dev_ptr(idx, torch.int32),
+                                                _lib.dev_ptr(counts, torch.int32), n, net._prec(precision, role), float(sigma_scale), _lib.dev_ptr(out),
+                                                _lib.stream_ptr()), "nm_mlp_forward_listed")
+    if stats is not None:
+        stats['evaluated'] = stats.get('evaluated', 0) + int(counts[0].item())
+        stats['total'] = stats.get('total', 0) + n
+    return out.reshape(*shp, 4)

@@ -213,7 +213,8 @@ def human_march_rays(human_net, o, d, near, far, samples_per_ray, mesh, eps, sig
     shortens them and RAISES the transmittance, so the cut is decided on the product of the human factors over the merged intervals:
     the merged list's transmittance can only be lower than that (the foreign samples' own factors are <= 1 + 1e-10), and what is skipped
     weighs < eps in the composite.  Without `dz` (render_smpl_nerf: the list is composited alone) the list's own intervals.  Every
-    evaluated sample is bit-identical to human_pass_rays' (per-sample arithmetic; tests/test_hip_march.py)."""
+    evaluated sample is bit-identical to human_pass_rays' (per-sample arithmetic; tests/test_hip_march.py).  With an occupancy grid on the
+    net (occupancy.attach, K11b) a chunk evaluates only its occupied canonical points; the others keep raw = 0."""
     _lib.require_gpu()
     R, S = o.shape[0], int(samples_per_ray)
     dev = o.device
@@ -224,16 +225,22 @@ def human_march_rays(human_net, o, d, near, far, samples_per_ray, mesh, eps, sig
     d = d.contiguous()
     live = torch.arange(R, device=dev)
     s0, evaluated, launches = 0, 0, 0
+    grid = occupancy.grid_of(human_net)
+    occ_stats = {} if grid is not None else None
     while s0 < S and live.numel() > 0:
         c = min(chunk, S - s0)
         a = s0 - 1 if (s0 + c == S and c == 1) else s0                               # a lone last sample takes its predecessor along
         b = min(S, s0 + c + 1)
         can_pts, can_dirs, _ = ray_utils.warp_to_canonical_dev(pts[live, a:b].contiguous(), mesh)
         k = s0 - a
-        out = human_net(can_pts[:, k:k + c].contiguous(), can_dirs[:, k:k + c].contiguous(), precision=precision, sigma_scale=sigma_scale,
-                        role='shading')
+        if grid is None:
+            out = human_net(can_pts[:, k:k + c].contiguous(), can_dirs[:, k:k + c].contiguous(), precision=precision, sigma_scale=sigma_scale,
+                            role='shading')
+            evaluated += live.numel() * c
+        else:                                                                       # the chunk's occupied canonical points only (K11b)
+            out = occupancy.forward_points(human_net, can_pts[:, k:k + c].contiguous(), can_dirs[:, k:k + c].contiguous(), precision=precision,
+                                           sigma_scale=sigma_scale, role='shading', stats=occ_stats)
         raw[live, s0:s0 + c] = out
-        evaluated += live.numel() * c
         launches += 1
         s0 += c
         if s0 >= S or eps <= 0:
@@ -245,6 +252,9 @@ def human_march_rays(human_net, o, d, near, far, samples_per_ray, mesh, eps, sig
         live = live[T[live] >= eps]
         # (march_pass_rays' rule: short chunks while rays are being cut, doubling when nothing happens)
         chunk = max(TERMINATION_MIN_CHUNK, chunk // 2) if live.numel() < 0.98 * n_live else chunk * 2
+    if occ_stats is not None:
+        evaluated = occ_stats.get('evaluated', 0)
+        _note(trace, occupancy_human={'evaluated': evaluated, 'total': R * S})
     if stats is not None:
         stats['human_evaluated'] = stats.get('human_evaluated', 0) + evaluated
         stats['human_total'] = stats.get('human_total', 0) + R * S
@@ -404,15 +414,31 @@ def human_pass_rays(human_net, o, d, near, far, samples_per_ray, mesh=None, rend
     dev = o.device
     human_net._guard(o, d, near)
     posed = not render_can
+    grid = occupancy.grid_of(human_net)
     raw = torch.empty((R, S, 4), device=dev, dtype=torch.float32)
     z = torch.empty((R, S), device=dev, dtype=torch.float32)
-    ws = _ws(_lib.lib().nm_render_rays_human_workspace_floats(R, S, int(posed)), dev)
     t_vals = torch.linspace(0., 1., steps=S, device=dev)
-    _lib.check(_lib.lib().nm_render_rays_human(
-        human_net.handle(), mesh.handle if posed else None, _lib.dev_ptr(mesh.T, torch.float64, 'T') if posed else None, _lib.dev_ptr(o.contiguous()),
-        _lib.dev_ptr(d.contiguous()), _lib.dev_ptr(near.reshape(-1).contiguous()), _lib.dev_ptr(far.reshape(-1).contiguous()), R, S, _lib.dev_ptr(t_vals), 1,
-        float(sigma_scale), human_net._prec(precision, 'shading'), _lib.dev_ptr(ws), _lib.dev_ptr(raw), _lib.dev_ptr(z), None, None, None, _lib.stream_ptr()),
-        "nm_render_rays_human")
+    if grid is None:
+        ws = _ws(_lib.lib().nm_render_rays_human_workspace_floats(R, S, int(posed)), dev)
+        _lib.check(_lib.lib().nm_render_rays_human(
+            human_net.handle(), mesh.handle if posed else None, _lib.dev_ptr(mesh.T, torch.float64, 'T') if posed else None, _lib.dev_ptr(o.contiguous()),
+            _lib.dev_ptr(d.contiguous()), _lib.dev_ptr(near.reshape(-1).contiguous()), _lib.dev_ptr(far.reshape(-1).contiguous()), R, S, _lib.dev_ptr(t_vals), 1,
+            float(sigma_scale), human_net._prec(precision, 'shading'), _lib.dev_ptr(ws), _lib.dev_ptr(raw), _lib.dev_ptr(z), None, None, None, _lib.stream_ptr()),
+            "nm_render_rays_human")
+    else:
+        # empty-space skipping (occupancy.py, K11b): the grid is tested on the canonical points -- o + d z (canonical render) or the warped
+        # points (posed); skipped samples keep raw = 0.  Same workspace prefix as nm_render_rays_human (the trace below reads it).
+        grid.check_device(dev)
+        counts = torch.zeros(2, device=dev, dtype=torch.int32)
+        ws = _ws(_lib.lib().nm_render_rays_human_occ_workspace_floats(R, S, int(posed)), dev)
+        _lib.check(_lib.lib().nm_render_rays_human_occ(
+            human_net.handle(), mesh.handle if posed else None, _lib.dev_ptr(mesh.T, torch.float64, 'T') if posed else None,
+            _lib.dev_ptr(grid.bits, torch.int32), grid.res, grid.box_c(), _lib.dev_ptr(o.contiguous()), _lib.dev_ptr(d.contiguous()),
+            _lib.dev_ptr(near.reshape(-1).contiguous()), _lib.dev_ptr(far.reshape(-1).contiguous()), R, S, _lib.dev_ptr(t_vals), 1, float(sigma_scale),
+            human_net._prec(precision, 'shading'), _lib.dev_ptr(ws), _lib.dev_ptr(raw), _lib.dev_ptr(z), _lib.dev_ptr(counts, torch.int32), None, None, None,
+            _lib.stream_ptr()), "nm_render_rays_human_occ")
+        if trace is not None:
+            _note(trace, occupancy_human={'evaluated': int(counts[0].item()), 'total': R * S})
     if trace is not None:
         if posed:
             n3 = (R * S * 3 + 3) & ~3
@@ -502,8 +528,9 @@ def render_hybrid_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far,
     are marched, each on the transmittance its samples have in the MERGED list (merged_intervals: the body's factors over the merged
     intervals bound the merged transmittance from above; behind the body the background sees its own x the body's): a pixel moves
     by < 2 eps, for bodies of any opacity (tests/test_hip_march.py: opaque and semi-transparent).
-    The plain case (no trace, no replay, no termination) is ONE C call per batch: render_hybrid_rays_fused, bit-identical."""
-    if TERMINATION_EPS <= 0 and trace is None and given is None and not _occupancy_on(coarse_bkg, fine_bkg):
+    The plain case (no trace, no replay, no termination, no occupancy grid on any of the nets) is ONE C call per batch: render_hybrid_rays_fused,
+    bit-identical."""
+    if TERMINATION_EPS <= 0 and trace is None and given is None and not _occupancy_on(coarse_bkg, fine_bkg) and occupancy.grid_of(human_net) is None:
         return render_hybrid_rays_fused(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far, posed_verts, mesh, samples_per_ray,
                                         importance_samples_per_ray, white_bkg, geo_threshold, precision)
     R = o.shape[0]
