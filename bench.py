@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- rays/s of the NeuMan ray-march hot path on MI355X (BASELINE.json metric, config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment launches itself: it checks that N devices are
@@ -17,14 +17,19 @@ inside the timed region; total work is fixed, so `scaling` is "strong".
 depth, as render_vanilla_rays hands them to its caller -- as DIR/rgb.npy [640000, 3] and DIR/depth.npy [640000] in float32.
 The nets are seeded and the rays fixed, so two builds run with the same arguments can be compared output for output.
 
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the dump if asked, and the JSON line with
+`value`, `ms_per_step`, the `roofline` figures (HIP events of the timed launches) and `multi_gpu`.  `--full` adds everything
+that takes runs of its own -- `other_precisions`, `parity_vs_oracle`, `parity_vs_reference`, `other_workloads` and `cpu_baseline`
+(N = 1 only, several minutes of CPU and GPU time); without it those keys are null and `cpu_baseline` is absent.
+
 Precision (`--precision`, default "mixed" = the package default): the coarse pass, whose compositing weights place the
 importance samples, runs split-fp16 x3 (float32-class sigma: the inverse CDF amplifies a coarse-pass error by 1 / pdf);
 the fine pass, whose output is composited into the frame, runs the 16-bit fixed-point limbs on the i8 MFMA.  Sample
 positions are bit-identical to the all-fp16x3 path and every pixel stays within 1e-4 of the oracle on identical samples
-(tests/test_hip_render.py); the bench line also reports the all-fp16x3, all-bf16x3 and all-i8x3 frame rates measured in
-the same run (`other_precisions`).
+(tests/test_hip_render.py); with `--full` the bench line also reports the all-fp16x3, all-bf16x3 and all-i8x3 frame rates
+measured in the same run (`other_precisions`).
 
-Parity (`parity_vs_oracle`): the CPU oracle renders the first 4096 rays of this very frame for the CPU baseline; its pixels,
+Parity (`parity_vs_oracle`, `--full`): the CPU oracle renders the first 4096 rays of this very frame for the CPU baseline; its pixels,
 coarse weights and fine sample positions are kept and the device renders the same rays in the timed configuration.  Reported: RGB
 L-inf, PSNR, rays off by more than 1e-4, and the attribution of that deviation (oracle/attribution.py): (a) the device's shading
 pass on the ORACLE's sample positions and (a') the oracle's on the DEVICE's, both <= 1e-4 on every ray; (b) the coarse weights;
@@ -40,7 +45,7 @@ discards the result, render_utils.py:139-141): sigma is bit-identical, 17 % of t
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel -- the fine launch (163.84 M of the frame's
 245.76 M evaluations): algorithmic FLOPs (1,186,816 per MLP evaluation) / its launch time measured with HIP
 events on the launch stream, against the 2.5 PFLOP/s dense bf16 MFMA peak; `roofline_coarse` is the same for the
-coarse launch.  `cpu_baseline` times the CPU restatement of the reference (the numpy port under oracle/, kind "port") on
+coarse launch.  `cpu_baseline` (`--full`) times the CPU restatement of the reference (the numpy port under oracle/, kind "port") on
 a bounded prefix of the same frame, on this box's host cores (N = 1 only).
 """
 import argparse
@@ -351,13 +356,15 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--precision", default="mixed", choices=list(DTYPES))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure and check what takes runs of its own: other precisions, parity "
+                    "against the oracle and the reference, other workloads, CPU baseline (minutes; a plain run reports the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity legs scored against it")
     ap.add_argument("--no-other-precisions", action="store_true",
-                    help="skip the all-bf16x3 / all-i8x3 frame rates reported beside the headline")
+                    help="with --full: skip the all-bf16x3 / all-i8x3 frame rates and the other workloads reported beside the headline")
     ap.add_argument("--dist", action="store_true", help="initialise the RCCL process group and run the gather collective at world size 1 too "
                     "(what a single-GPU box can execute of the N > 1 path; tests/test_parallel_gpu.py)")
     ap.add_argument("--timed-only", action="store_true", help="profiling runs: nothing but the warm-up and the timed steps "
-                    "(no quality check, other precisions or CPU baseline), so every MLP launch rocprofv3 sees is a timed one")
+                    "(no quality check, other precisions or CPU baseline, even with --full), so every MLP launch a profiler sees is a timed one")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="process-group backend (nccl = RCCL; gloo only with --launch-check)")
     ap.add_argument("--launch-check", action="store_true", help="bring the process group up, assemble one dummy frame through the gather "
                     "and exit (no device needed with --backend gloo: the CPU-side test of the self-launch)")
@@ -517,7 +524,7 @@ def main():
             net.__dict__.pop('forward_rays', None)              # drop the event-recording wrappers
 
         others, parity, base, pvr = None, None, None, None
-        extras = args.precision != "fp32" and not args.timed_only
+        extras = args.full and args.precision != "fp32" and not args.timed_only
         if extras and world == 1 and not args.no_other_precisions:
             others = {}
             with torch.no_grad():

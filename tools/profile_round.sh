@@ -46,7 +46,7 @@ print(json.dumps(out['derived']))
 PY
 cd $R
 cp $OUT/bench_pmc_summary.json profiles/${TAG}_bench_pmc_summary.json 2>/dev/null     # bench.py reads `traffic` from here
-python bench.py --steps 5 --warmup 1 > $OUT/bench_line.json 2> $OUT/bench_stderr.log
+python bench.py --steps 5 --warmup 1 --full > $OUT/bench_line.json 2> $OUT/bench_stderr.log
 tail -c 1500 $OUT/bench_line.json
 cp $OUT/bench_kernel_stats.csv profiles/${TAG}_bench_kernel_stats.csv 2>/dev/null
 cp $OUT/bench_line.json profiles/${TAG}_bench_line.json 2>/dev/null
