@@ -479,7 +479,7 @@ int nm_merge_composite_lists(int k, const float* const* z, const float* const* r
  * the weights are written only when weights_out [R,S] != NULL.  Bit-identical to nm_composite + nm_importance_z. */
 int nm_importance_from_raw(const float* raw, const float* z_vals, const float* rays_d, int64_t R, int S, const float* u, int N, float* z_out,
                            float* weights_out, nm_stream_t stream);
-/* The intervals the samples of k <= 4 sorted lists per ray (z[l] [R,S[l]]) will be composited with ONCE MERGED: for every sample the distance
+/* The intervals the samples of k <= 32 sorted lists per ray (z[l] [R,S[l]]; its own limit, not nm_merge_composite_lists' 4: nothing is staged in LDS) will be composited with ONCE MERGED: for every sample the distance
  * to its successor in the stable merged order (ties: the earlier list first -- nm_merge_sorted's order, the reference's sort(cat(...)),
  * utils/render_utils.py:330-337, 441-448), 1e10 for the last sample of the merged list (:86) -> dz[l] [R,S[l]].  What an early-termination
  * cut is decided on before the lists are merged.  z / S / dz are HOST arrays of k entries. */

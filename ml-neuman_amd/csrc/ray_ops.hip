@@ -489,16 +489,19 @@ __global__ __launch_bounds__(256) void rows_kernel(const float* __restrict__ src
 }
 
 // ------------------------------------------------------------------------------------------------
-// For every sample of k <= 4 sorted lists per ray: the distance to its successor in the MERGED (stable, earlier list first) order of the
+// For every sample of k <= kMaxIntervalLists sorted lists per ray: the distance to its successor in the MERGED (stable, earlier list first) order of the
 // reference's sort(cat(...)) (render_utils.py:330-337, 441-448); the last sample of the merged list gets raw2outputs' 1e10 (:86).  The
 // successor of sample i of list a is the nearest of: its own list's sample i + 1, the first sample >= z of every LATER list (equal values
 // of a later list come after) and the first sample > z of every EARLIER list.  One thread per sample, binary searches in the other rows
 // (a row is at most a few hundred floats: L1 / L2 resident); nothing is sorted, nothing is written but dz.  Bound: HBM (4 B in, 4 B out).
 // ------------------------------------------------------------------------------------------------
+// Nothing of a list is staged in LDS or registers here (the kernel searches the other rows in global memory), so the list limit is this
+// kernel's own, not kMaxMergeLists: the multi-person renderer with early termination passes the background list and one per actor.
+constexpr int kMaxIntervalLists = 32;
 struct IntervalLists {
-    const float* z[kMaxMergeLists];
-    float* dz[kMaxMergeLists];
-    int S[kMaxMergeLists];
+    const float* z[kMaxIntervalLists];
+    float* dz[kMaxIntervalLists];
+    int S[kMaxIntervalLists];
     int k, S_total;
 };
 __global__ __launch_bounds__(256) void merged_intervals_kernel(const IntervalLists L, int64_t R) {
@@ -644,11 +647,11 @@ int nm_merge_composite_lists(int k, const float* const* z, const float* const* r
 }
 
 int nm_merged_intervals(int k, const float* const* z, const int* S, int64_t R, float* const* dz, nm_stream_t stream) {
-    NM_REQUIRE(k >= 1 && k <= kMaxMergeLists && z && S && dz, "nm_merged_intervals: 1 <= k <= %d lists (k=%d)", kMaxMergeLists, k);
+    NM_REQUIRE(k >= 1 && k <= kMaxIntervalLists && z && S && dz, "nm_merged_intervals: 1 <= k <= %d lists (k=%d)", kMaxIntervalLists, k);
     IntervalLists L;
     L.k = k;
     L.S_total = 0;
-    for (int l = 0; l < kMaxMergeLists; ++l) {
+    for (int l = 0; l < kMaxIntervalLists; ++l) {
         const bool on = l < k;
         L.z[l] = on ? z[l] : nullptr;
         L.dz[l] = on ? dz[l] : nullptr;

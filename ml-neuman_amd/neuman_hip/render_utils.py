@@ -110,7 +110,8 @@ def _transmittance_chunk(raw, z, dz, d, live, counts, R, s0, c, S, T):
 
 
 def merged_intervals(z_lists):
-    """For every sample of every list ([R, S_k] each, sorted per ray; k <= 4): the distance to its successor in the MERGED order of all the
+    """For every sample of every list ([R, S_k] each, sorted per ray; k <= 32, nm_merged_intervals' own limit -- the background list and up to
+    31 actors): the distance to its successor in the MERGED order of all the
     lists (stable, earlier list first -- the order of the reference's sort(cat(...)), render_utils.py:330-337, 441-448); the last
     sample of the merged list gets raw2outputs' 1e10 (render_utils.py:86).  -> one [R, S_k] tensor per list.  These are the
     intervals the samples will be composited with once the lists are merged: what an early-termination cut has to be decided on.

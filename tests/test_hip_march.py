@@ -222,7 +222,7 @@ def test_renderers_with_termination(body, which):
     assert (semi or he < 0.8 * ht) and e <= bound
 
 
-@pytest.mark.parametrize("sizes", [(256, 128), (320, 192, 192, 192), (7,), (5, 1, 3)])
+@pytest.mark.parametrize("sizes", [(256, 128), (320, 192, 192, 192), (7,), (5, 1, 3), (320, 192, 192, 192, 192), (256,) + (64,) * 5, (9,) * 32])
 def test_merged_intervals_equal_the_sorted_lists_differences(sizes):
     """render_utils.merged_intervals (nm_merged_intervals: binary searches, nothing sorted) against the definition: stable argsort of
     cat(lists) (ties: the earlier list first, the order of render_utils.py:330-337), differences of the sorted values, 1e10 at the end,
