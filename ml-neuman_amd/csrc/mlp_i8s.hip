@@ -18,9 +18,6 @@
 //
 // Reference semantics: models/vanilla.py Embedder.forward (:82-92), NeRF.forward (:120-152), Joiner.forward (:162-166).
 #include "mlp_i8as.h"
-#include <stdio.h>
-#include <stdlib.h>
-#include <vector>
 
 namespace {
 
@@ -44,22 +41,6 @@ __host__ __device__ constexpr int block_steps(int i) {
 }
 __host__ __device__ constexpr int block_pieces(int nsteps) { return (2 * nsteps + kWaves - 1) / kWaves; }   // 1 KB pieces per wave
 
-// -DNM_AS_PROF: cycle buckets per wave (s_memtime = shader cycles): 0 wait at the top-of-block barrier (own copies + the other waves),
-// 1 copy issue, 2 k-loop, 4 epilogue, 5 requantisation at the end of a stage, 6 encodings, 7 rest
-#ifdef NM_AS_PROF
-struct Prof {
-    unsigned long long t, acc[8];
-};
-#define PROF_DECL Prof P; P.t = __builtin_amdgcn_s_memtime(); for (int i_ = 0; i_ < 8; ++i_) P.acc[i_] = 0;
-#define PROF_TICK(b) { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); P.acc[b] += n_ - P.t; P.t = n_; }
-#define PROF_ARG , Prof& P
-#define PROF_PASS , P
-#else
-#define PROF_DECL
-#define PROF_TICK(b)
-#define PROF_ARG
-#define PROF_PASS
-#endif
 // ---- the weight ring.  Producer side: every wave copies its share (1 KB pieces i = w, w + 8, ..) of the block TWO ahead; consumer side:
 // all waves read every fragment of the current block.  Hand-over, once per block: each wave waits until its own pieces of the block it is
 // about to enter have landed (counted vmcnt: the pieces of the block after it stay in flight -- issue to landing is about 1 us, longer
@@ -85,14 +66,12 @@ __device__ __forceinline__ void ring_advance(Ring& R, int nsteps) {
 // enter flat block i of the tile; returns this lane's view of block i.  The copy of block i + 2 (into the slot block i - 1 has just given
 // up) is issued from inside the k-loop (ring_copy after k-steps 0, 2, 4): the texture path takes one 1 KB piece at a time, and eight
 // waves issuing theirs right after the barrier would all start their MFMAs late.
-__device__ __forceinline__ const uint4* ring_enter(Ring& R, int i PROF_ARG) {
-    PROF_TICK(4)
+__device__ __forceinline__ const uint4* ring_enter(Ring& R, int i) {
     const int np1 = block_pieces(block_steps(i + 1));
     if (np1 == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
     else if (np1 == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    PROF_TICK(0)
     const uint4* cur = R.rd + R.slot * kSlotU4;
     R.refill = R.slot == 0 ? kSlots - 1 : R.slot - 1;                  // the slot of block i - 1 = of block i + 2
     R.slot = R.slot == kSlots - 1 ? 0 : R.slot + 1;
@@ -202,14 +181,11 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
                                                                                         // out of the tile loop and spilled)
     const int64_t ntiles = (a.n + kTile - 1) / kTile;
     for (int i = lane; i < kPWaveU4; i += 64) pw[i] = make_uint4(0, 0, 0, 0);          // pad slots: finite once
-    PROF_DECL
 
 #pragma unroll 1
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const int64_t row0 = tile * kTile + w * kRows;                                  // this wave's first sample (rows past n: clamped)
-        PROF_TICK(7)
         fill_pe_wave(pw, false, a, row0, lane);
-        PROF_TICK(6)
         X8 X;
         float sx;                                                                       // the row scale of X: x = sx * (256 hi + lo) * unit[feature]
         // ---------------- stage 0: encodings only (split bf16), ReLU
@@ -218,18 +194,15 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
             float m = 0.f;
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
-                const uint4* ws = ring_enter(R, b PROF_PASS);
+                const uint4* ws = ring_enter(R, b);
                 bias16(f[b], bias + nm::stage_b_off(0) + 32 * b);
                 k_bf<4, true>(f[b], pw, g, s, ws, &R);
-                PROF_TICK(2)
                 m = max16<true>(m, f[b]);
             }
-            PROF_TICK(4)
             const float M = row_max(m), inv = inv_of(M);
 #pragma unroll
             for (int b = 0; b < 8; ++b) quant16<true>(f[b], inv, X.h[b], X.l[b]);
             sx = scale_of(M);
-            PROF_TICK(5)
         }
         // ---------------- stages 1..7: 256 -> 256, ReLU; stage 5 adds the position encoding (four more ring blocks of two output blocks each)
 #pragma unroll 1
@@ -241,7 +214,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
             i32x16 tp;                                                                  // block b - 1, dequantised under block b's MFMAs
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
-                const uint4* ws = ring_enter(R, i0 + b PROF_PASS);
+                const uint4* ws = ring_enter(R, i0 + b);
                 if (b == 0) {
                     k_i8<8>(tp, X, ws, R);
                 } else {
@@ -249,40 +222,33 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
                     k_i8_impl<8, true>(t, X, ws, R, f[b - 1], tp, bias + 256 * st + 32 * (b - 1), sxin, m);
                     tp = t;
                 }
-                PROF_TICK(2)
             }
             dequant16(f[7], tp, sxin, bias + 256 * st + 32 * 7);
             if (st == 5) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
-                    const uint4* ws = ring_enter(R, 48 + u PROF_PASS);
+                    const uint4* ws = ring_enter(R, 48 + u);
                     k_bf<4, true>(f[2 * u], pw, g, s, ws, &R, 0);
                     k_bf<4, true>(f[2 * u + 1], pw, g, s, ws + 4 * kStepU4, &R, 2);
-                    PROF_TICK(2)
                 }
                 m = 0.f;                                                                // (the running maximum was taken before the encodings)
 #pragma unroll
                 for (int b = 0; b < 7; ++b) m = max16<true>(m, f[b]);
             }
             m = max16<true>(m, f[7]);
-            PROF_TICK(4)
             const float M = row_max(m), inv = inv_of(M);
 #pragma unroll
             for (int b = 0; b < 8; ++b) quant16<true>(f[b], inv, X.h[b], X.l[b]);
             sx = scale_of(M);
-            PROF_TICK(5)
             if (st == 5 && !(PLAIN && a.sigma_only == 2)) {
-                PROF_TICK(7)
                 fill_pe_wave(pw, true, a, row0, lane);                                  // the position encoding is done with: direction encoding
-                PROF_TICK(6)
             }
         }
         if (PLAIN && a.sigma_only == 2) {
             // ---------------- the plain head: rows 0..3 of block 68 = output_linear's (r, g, b, sigma)
             i32x16 t;
             f32x16 fo;
-            k_i8<8>(t, X, ring_enter(R, 68 PROF_PASS), R);
-            PROF_TICK(2)
+            k_i8<8>(t, X, ring_enter(R, 68), R);
             dequant16(fo, t, sx * (256.f * kappa[8]), bias + nm::stage_b_off(8) + 256);
             const float* up = A.consts8 + nm::stage_b_off(8) + 256;                     // the four rows' units
             const int64_t i = row0 + s;
@@ -298,8 +264,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
             {
                 i32x16 t;
                 f32x16 fa;
-                k_i8<8>(t, X, ring_enter(R, 68 PROF_PASS), R);
-                PROF_TICK(2)
+                k_i8<8>(t, X, ring_enter(R, 68), R);
                 dequant16(fa, t, sxin, bias + nm::stage_b_off(8) + 256);
                 sigma = fa[0] * u_sigma;
             }
@@ -308,17 +273,14 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
 #pragma unroll
             for (int b = 0; b < 8; ++b) {                                               // (the riding dequantisation measured no gain here)
                 i32x16 t;
-                k_i8<8>(t, X, ring_enter(R, 69 + b PROF_PASS), R);
-                PROF_TICK(2)
+                k_i8<8>(t, X, ring_enter(R, 69 + b), R);
                 dequant16(f[b], t, sxin, bias + nm::stage_b_off(8) + 32 * b);
                 m = max16<false>(m, f[b]);
             }
-            PROF_TICK(4)
             const float M = row_max(m), inv = inv_of(M);
 #pragma unroll
             for (int b = 0; b < 8; ++b) quant16<false>(f[b], inv, X.h[b], X.l[b]);
             sx = scale_of(M);
-            PROF_TICK(5)
         }
         // ---------------- stage 9: views layer, K = feature(256) ++ d_pe(32), N = 128, ReLU
         {
@@ -328,26 +290,22 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 i32x16 t;
-                const uint4* ws = ring_enter(R, 77 + b PROF_PASS);
+                const uint4* ws = ring_enter(R, 77 + b);
                 k_i8<8>(t, X, ws, R);
-                PROF_TICK(2)
                 dequant16(f[b], t, sxin, bias + nm::stage_b_off(9) + 32 * b);
                 k_bf<2>(f[b], pw, g, s, ws + 8 * kStepU4);
                 m = max16<true>(m, f[b]);
             }
-            PROF_TICK(4)
             const float M = row_max(m), inv = inv_of(M);
 #pragma unroll
             for (int b = 0; b < 4; ++b) quant16<true>(f[b], inv, X.h[b], X.l[b]);
             sx = scale_of(M);
-            PROF_TICK(5)
         }
         // ---------------- stage 10: rgb (rows 0..2 of one block), K = 128
         {
             i32x16 t;
             f32x16 fr;
-            k_i8<4>(t, X, ring_enter(R, 81 PROF_PASS), R);
-            PROF_TICK(2)
+            k_i8<4>(t, X, ring_enter(R, 81), R);
             dequant16(fr, t, sx * (256.f * kappa[10]), bias + nm::stage_b_off(10));
             const int64_t i = row0 + s;
             if (g == 0 && i < a.n)
@@ -356,11 +314,6 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
                                 sigma * a.sigma_scale);
         }
     }
-#ifdef NM_AS_PROF
-    PROF_TICK(7)
-    if (lane == 0 && a.prof)
-        for (int i = 0; i < 8; ++i) a.prof[((size_t)blockIdx.x * kWaves + w) * 8 + i] = P.acc[i];
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                    // the copy started for a tile that never comes
 }
 
@@ -393,34 +346,8 @@ int launch_mlp_i8s(const MlpLaunch& L, const void* image8, const float* pts, con
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
     }
     const int grid = (int)(ntiles < cus ? ntiles : cus);
-    if (getenv("NEUMAN_I8S_DEBUG")) {
-        int nb = -1;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, nerf_mlp_i8s_kernel<false>, kWaves * 64, 0);
-        fprintf(stderr, "nerf_mlp_i8s_kernel: occupancy %d blocks/CU (%s), grid %d, cus %d\n", nb, hipGetErrorString(e), grid, cus);
-    }
-#ifdef NM_AS_PROF
-    static unsigned long long* d_prof = nullptr;
-    const size_t nprof = (size_t)grid * kWaves * 8;
-    if (!d_prof) (void)hipMalloc(&d_prof, (size_t)1024 * kWaves * 8 * 8);
-    (void)hipMemsetAsync(d_prof, 0, nprof * 8, stream);
-    a.prof = d_prof;
-#endif
     if (L.plain_head) hipLaunchKernelGGL(nerf_mlp_i8s_kernel<true>, dim3(grid), dim3(kWaves * 64), 0, stream, A);
     else hipLaunchKernelGGL(nerf_mlp_i8s_kernel<false>, dim3(grid), dim3(kWaves * 64), 0, stream, A);
-#ifdef NM_AS_PROF
-    if (n > 1000000) {
-        std::vector<unsigned long long> h(nprof);
-        (void)hipStreamSynchronize(stream);
-        (void)hipMemcpy(h.data(), d_prof, nprof * 8, hipMemcpyDeviceToHost);
-        static const char* names[8] = {"top barrier", "copy issue", "k-loop", "-", "epilogue", "requantise", "encodings", "rest"};
-        double acc[8] = {0}, tot = 0;
-        for (size_t i = 0; i < nprof; ++i) acc[i & 7] += (double)h[i];
-        for (int i = 0; i < 8; ++i) tot += acc[i];
-        fprintf(stderr, "mean cycles per wave %.0f:", tot / (grid * (double)kWaves));
-        for (int i = 0; i < 8; ++i) fprintf(stderr, "  %s %.1f%%", names[i], 100.0 * acc[i] / tot);
-        fprintf(stderr, "\n");
-    }
-#endif
     return check_launch("nerf_mlp_i8s_kernel");
 }
 

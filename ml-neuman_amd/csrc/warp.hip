@@ -351,7 +351,6 @@ constexpr int kChunk = 512;
 // long as its slowest sample's chain of dependent loads (92 k ray samples: 0.95 ms at 16, 32, 64 or 128 samples per wave alike), so a lane should
 // not queue a second sample behind its first while SIMDs idle: one sample per lane up to 262 k samples (184 k points: 0.97 ms against 1.27 at 128).
 inline int chunk_for(int64_t N) {
-    if (const char* e = getenv("NEUMAN_SEARCH_CHUNK")) { const int v = atoi(e); if (v >= 8 && v <= kChunk) return v; }     // (tools: sweeps)
     int64_t c = (N / 4096 + 63) / 64 * 64;
     return (int)(c < 64 ? 64 : c > kChunk ? kChunk : c);
 }

@@ -32,9 +32,6 @@ PATCH_SIZE = 32                                    # :8
 CANONICAL_CAMERA_DIST = 3.0                        # :13
 
 
-BATCH_NET_CALLS = os.environ.get('NEUMAN_BATCH_NET_CALLS', '1') != '0'     # the iteration's five human-network evaluations as one call
-
-
 def _occupancy(raw):
     """1 - exp(-relu(sigma)) of a raw network output [..., 4]: the opacity of a unit interval"""
     return 1 - torch.exp(-torch.relu(raw.reshape(-1, 4)[:, 3]))
@@ -113,8 +110,7 @@ class HumanNeRFLoss:
         """coarse_human_net on every (points, directions) set of an iteration in ONE call.  The reference calls the network five times
         (:276 the rays' samples, :286 / :299 / :331 / :364 the regularisers' points); a sample's output does not depend on what else is in
         the batch, and `cat` / `split` are differentiable, so one forward, one backward-data chain and one set of backward-weights products
-        serve all of them (a fifth of the launches; the parameter gradients are the same sums in another order).  BATCH_NET_CALLS = False:
-        one call per set."""
+        serve all of them (a fifth of the launches; the parameter gradients are the same sums in another order)."""
         net = self.net.coarse_human_net
         outs = [None] * len(queries)
         # a query set that asks about the FIRST set's points again (the colour-range term: the same tensor, other directions) does not need the trunk a
@@ -126,7 +122,7 @@ class HumanNeRFLoss:
             if pair is not None:
                 outs[0], outs[twin] = pair
         rest = [i for i in range(len(queries)) if outs[i] is None]
-        if not BATCH_NET_CALLS or len(rest) == 1:
+        if len(rest) == 1:
             for i in rest:
                 outs[i] = net(*queries[i])
         elif rest:

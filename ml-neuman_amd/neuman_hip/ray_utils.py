@@ -6,7 +6,6 @@ runs in libneuman_hip.so.  Functions that the reference defines on torch tensors
 on CPU tensors -- there is no host fallback.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -460,9 +459,6 @@ class _BaryFn(torch.autograd.Function):
         return g_v, None, None
 
 
-BARY_KERNELS = os.environ.get('NEUMAN_BARY_KERNELS', '1') != '0'       # 0: the reference's torch lines under autograd (the check of the kernels)
-
-
 # The differentiable warp is called once per training iteration with the SAME face array and moved vertices: the device copies of the faces and the
 # search handle are kept (keyed by the face array object) and the handle is updated in place -- building a Mesh costs eight allocations, a
 # host-to-device copy of the faces, three read-backs and as many frees, every one of which stalls the queue the iteration's kernels wait in.
@@ -498,7 +494,7 @@ def _closest_barycentric(p, verts, f3, mesh=None):
     mesh = mesh or Mesh(verts.detach(), f3.to(torch.int32), None, verts.device)
     signed_dist, f_id, closest = signed_distance_dev(p, mesh)
     f_id = f_id.long()
-    if BARY_KERNELS and verts.dtype == torch.float32:
+    if verts.dtype == torch.float32:
         return _BaryFn.apply(verts, f3[f_id].to(torch.int32).contiguous(), closest.contiguous()), f_id, signed_dist
     return _barycentric_torch(verts[f3[f_id]], closest), f_id, signed_dist
 
@@ -506,7 +502,7 @@ def _closest_barycentric(p, verts, f3, mesh=None):
 def _barycentric_torch(corners, p):
     """Barycentric coordinates of points p [N,3] in triangles corners [N,3,3] as ratios of signed areas: the sub-triangle opposite corner k
     (spanned from corner k+1 to corner k+2 and to p), projected on the triangle's normal, over the triangle's own -- the quantity
-    ray_utils.py:73-84 computes; plain torch under autograd (the check of nm_bary_forward / _backward, and the path for non-float32 vertices)."""
+    ray_utils.py:73-84 computes; plain torch under autograd (the path for non-float32 vertices)."""
     nxt, prv = corners.roll(-1, 1), corners.roll(-2, 1)
     normal = torch.linalg.cross(corners[:, 1] - corners[:, 0], corners[:, 2] - corners[:, 0])
     sub = torch.linalg.cross(prv - nxt, p[:, None, :] - nxt)

@@ -813,8 +813,7 @@ class _ViewsHead(torch.autograd.Function):
 def two_views_ok(joiner, n):
     """can `two_views` serve n points of this net?  (the fused fp16-storage step: the only form whose forward hands out feature_linear's output)"""
     return (_fused_ok(joiner) and STORE16 and FUSED_BACKWARD and (n + 3) // 4 * 4 >= STORE16_MIN_ROWS and joiner.pos_pe.out_dim <= 64
-            and joiner.pos_pe.include_input and joiner.dir_pe.include_input          # (include_input=False: two plain calls through _full_input)
-            and os.environ.get("NEUMAN_TWO_VIEWS", "1") != "0")
+            and joiner.pos_pe.include_input and joiner.dir_pe.include_input)         # (include_input=False: two plain calls through _full_input)
 
 
 def two_views(joiner, pts, dirs, dirs2):

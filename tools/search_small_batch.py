@@ -1,5 +1,5 @@
 """The closest-point search at a TRAINING iteration's sizes (the human trainer: 92 k ray samples against the posed body, 184 k canonical + random box points
-against the canonical one): time per call, for chunk-size sweeps (NEUMAN_SEARCH_CHUNK).  Prints one JSON line; the checksums pin the outputs."""
+against the canonical one): time per call.  Prints one JSON line; the checksums pin the outputs."""
 import json
 import os
 import sys
@@ -42,5 +42,5 @@ def med(fn, n=9):
 
 a_ms, a = med(lambda: ray_utils.signed_distance_dev(ray_pts, mesh))
 b_ms, b = med(lambda: ray_utils.signed_distance_dev(box_pts, mesh))
-print(json.dumps({"chunk": os.environ.get("NEUMAN_SEARCH_CHUNK"), "ray_samples": ray_pts.shape[0], "ray_ms": a_ms, "ray_plus_box_points": box_pts.shape[0], "box_ms": b_ms,
+print(json.dumps({"ray_samples": ray_pts.shape[0], "ray_ms": a_ms, "ray_plus_box_points": box_pts.shape[0], "box_ms": b_ms,
                   "checksums": [float(a[0].double().sum()), float(a[2].double().sum()), float(b[0].double().sum()), int(b[1].long().sum())]}))
