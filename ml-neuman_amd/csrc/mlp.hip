@@ -64,6 +64,17 @@ __global__ __launch_bounds__(kThreads, 2) void nerf_mlp_kernel(const MlpArgs a_i
         const_cast<uint4*>(a.wpack), 0, (int)(nm::kWeightBytes + nm::kWeightPadBytes), 0x00020000);
     const int voff = lane * 16;                                   // the only per-lane part of a weight address
     const int64_t ntiles = (a.n + kTileM - 1) / kTileM;
+    // SAVE (a training forward): a sample with a NaN / Inf coordinate or direction component comes out NaN on all four outputs, as the reference's
+    // sin / cos of it do -- the clamps of the operand split (split8) would otherwise hand the trainer's NaN check a finite loss.  Output stage only.
+    auto train_out = [&](int64_t i, float4 v) {
+        const float* p = a.pts + i * 3;
+        const float* q = a.dirs + i * 3;
+        bool bad = false;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) bad |= (__float_as_uint(p[c]) & 0x7F800000u) == 0x7F800000u || (__float_as_uint(q[c]) & 0x7F800000u) == 0x7F800000u;
+        const float nan = __uint_as_float(0x7FC00000u);
+        return bad ? make_float4(nan, nan, nan, nan) : v;
+    };
 
     // wave-uniform offsets of this wave's weight streams (bytes into the image)
     auto wo = [](int st, int blk) { return (int)nm::stage_w_off(st) + blk * nm::stage_shape(st).steps * nm::kStepBytes; };
@@ -172,6 +183,9 @@ __global__ __launch_bounds__(kThreads, 2) void nerf_mlp_kernel(const MlpArgs a_i
                 const int64_t i = base + 32 * w + s;
                 if (g == 0 && i < a.n) {
                     const float os = acc2out(8);
+                    if (SAVE)                                     // (the plain-head net's training forward)
+                        reinterpret_cast<float4*>(a.out)[i] = train_out(i, make_float4(aacc[0][0] * os, aacc[0][1] * os, aacc[0][2] * os, aacc[0][3] * os * a.sigma_scale));
+                    else
                     reinterpret_cast<float4*>(a.out)[sample_record(a, i)] =
                         a.sigma_only == 2 ? make_float4(aacc[0][0] * os, aacc[0][1] * os, aacc[0][2] * os, aacc[0][3] * os * a.sigma_scale)   // vanilla.py:145
                                           : make_float4(0.f, 0.f, 0.f, aacc[0][0] * os * a.sigma_scale);
@@ -304,6 +318,10 @@ __global__ __launch_bounds__(kThreads, 2) void nerf_mlp_kernel(const MlpArgs a_i
             k_run<1, PREC>(racc, W, wsrc, voff, so_s10, so_s0, lds + H_BASE + g * kChunkU4 + 32 * w + s, sh.steps);
             bias_prefetch(B, a.bias + nm::stage_b_off(0) + 32 * w, g);
             const int64_t i = base + 32 * w + s;
+            if (SAVE) {
+                if (g == 0 && i < a.n)
+                    reinterpret_cast<float4*>(a.out)[i] = train_out(i, make_float4(racc[0][0] * acc2out(10), racc[0][1] * acc2out(10), racc[0][2] * acc2out(10), sigma * a.sigma_scale));
+            } else
             if (g == 0 && i < a.n)                                // rows 0,1,2 = regs 0,1,2 of the g == 0 half
                 reinterpret_cast<float4*>(a.out)[sample_record(a, i)] = make_float4(racc[0][0] * acc2out(10), racc[0][1] * acc2out(10), racc[0][2] * acc2out(10), sigma * a.sigma_scale);
         }

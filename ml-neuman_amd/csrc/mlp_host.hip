@@ -1,11 +1,13 @@
 // Host side of the MLP entry points: weight packing (split bf16, MFMA fragment order), the opaque
 // handle, and the dispatch of nm_mlp_forward* onto the MFMA kernel (mlp.hip) or the exact-f32
 // validation kernel (mlp_ref.hip).  Also the library-level basics (version, errors, device count).
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "common.h"
@@ -44,12 +46,13 @@ static inline float bf16_to_f32(uint16_t h) {
 }
 
 // ---- fp16 helpers (round to nearest even, subnormals kept, overflow saturates to the largest finite value) -----------------
+// (the host packers refuse a net with a non-finite parameter before anything is packed: check_finite)
 static inline uint16_t f32_to_f16(float f) {
     uint32_t u;
     memcpy(&u, &f, 4);
     const uint32_t sign = (u >> 16) & 0x8000u;
     u &= 0x7FFFFFFFu;
-    if (u >= 0x7F800000u) return (uint16_t)(sign | 0x7BFFu);            // inf / nan never occur in a weight image: saturate
+    if (u >= 0x7F800000u) return (uint16_t)(sign | 0x7BFFu);            // inf / nan never reach a host-packed image (check_finite): saturate
     if (u >= 0x477FF000u) return (uint16_t)(sign | 0x7BFFu);            // >= 65520 rounds past the largest fp16: saturate
     if (u < 0x38800000u) {                                              // below 2^-14: subnormal fp16 (or zero)
         if (u < 0x33000000u) return (uint16_t)sign;                     // < 2^-25: rounds to zero
@@ -95,6 +98,38 @@ static int validate_desc(const nm_mlp_desc* d) {
     NM_REQUIRE(d->pos_n_freqs >= 1 && d->pos_n_freqs <= 10, "nm_mlp: pos_n_freqs %d outside 1..10", d->pos_n_freqs);
     NM_REQUIRE(d->dir_n_freqs >= 1 && d->dir_n_freqs <= 4, "nm_mlp: dir_n_freqs %d outside 1..4", d->dir_n_freqs);
     NM_REQUIRE(d->plain_head == 0 || d->plain_head == 1, "nm_mlp: plain_head must be 0 or 1, got %d", d->plain_head);
+    return NM_OK;
+}
+
+// A NaN or Inf parameter (a diverged optimiser step) makes the reference's network output NaN.  No packed image can say that per weight -- the i8
+// image rounds to integers, fmaxf drops a NaN from a row maximum, the fp16 image saturates -- so a host packer given one would write a finite image
+// and the frame would be finite garbage.  The packers and nm_mlp_create refuse such a net instead, naming the tensor, before anything is written
+// or allocated.  (nm_mlp_refresh_f16 rebuilds the fp16 image on the device without asking the host: its kernels hand a NaN / Inf on.)
+static int check_finite(const char* who, const nm_mlp_desc* d, const float* const* P) {
+    const int kpe = 3 + 6 * d->pos_n_freqs, kdpe = 3 + 6 * d->dir_n_freqs;
+    static const char* const head_names[4] = {"views_linears.0", "feature_linear", "alpha_linear", "rgb_linear"};
+    const int64_t head_w[4] = {128 * (int64_t)(256 + kdpe), 256 * 256, 256, 3 * 128}, head_b[4] = {128, 256, 1, 3};
+    for (int i = 0; i < (d->plain_head ? 18 : 24); ++i) {
+        const int l = i >> 1, is_bias = i & 1;
+        char name[40];
+        int64_t count;
+        if (l < 8) {
+            snprintf(name, sizeof(name), "pts_linears.%d.%s", l, is_bias ? "bias" : "weight");
+            count = is_bias ? 256 : 256 * (int64_t)(l == 0 ? kpe : (l == 5 ? kpe + 256 : 256));
+        } else if (d->plain_head) {
+            snprintf(name, sizeof(name), "output_linear.%s", is_bias ? "bias" : "weight");
+            count = is_bias ? 4 : 4 * 256;
+        } else {
+            snprintf(name, sizeof(name), "%s.%s", head_names[l - 8], is_bias ? "bias" : "weight");
+            count = is_bias ? head_b[l - 8] : head_w[l - 8];
+        }
+        for (int64_t k = 0; k < count; ++k) {
+            uint32_t u;
+            memcpy(&u, &P[i][k], 4);
+            NM_REQUIRE((u & 0x7F800000u) != 0x7F800000u, "%s: %s[%lld] = %g is not finite (host_params[%d]); a net with a NaN / Inf parameter has no weight image",
+                       who, name, (long long)k, (double)P[i][k], i);
+        }
+    }
     return NM_OK;
 }
 
@@ -201,31 +236,48 @@ static void pack_image(const nm_mlp_desc* d, const float* const* P, uint8_t* img
 // (round 6: kScaleSlices workgroups per stage instead of one -- 45 -> a few microseconds in front of every training forward; the largest magnitude is
 //  the same number in whatever order it is found, so the image is bit-identical.  work = [kStages] running maxima as uint bits | [kStages] arrival counters,
 //  zeroed by the caller; the last slice of a stage to arrive turns its maximum into the scale.)
+// A NaN or Inf parameter (a diverged optimiser step) must reach the trainer's NaN check as a NaN loss, as in the reference, and this path cannot ask
+// the host.  The forward kernel clamps its activations (split8), so a NaN accumulator of a hidden layer would come out finite: instead the stage's
+// maximum is taken over the magnitudes' BIT PATTERNS -- finite < Inf < NaN as unsigned integers, and among finite magnitudes the float order, so a
+// finite net's scale is the same number -- a non-finite bias of the stage counts into it, the stage's scale is then NaN, and f16_bias_kernel turns
+// EVERY factor of the table into NaN, the output factors of stages 8 and 10 among them: all four outputs of every sample are NaN.
 constexpr int kScaleSlices = 16;
+__device__ __forceinline__ float stage_bias(const DevParams& P, int plain_head, int st, int r) {
+    if (st <= 7) return P.p[P_PTS_W + 2 * st + 1][r];
+    if (plain_head) return (st == 8 && r >= 256 && r < 260) ? P.p[P_OUT_B][r - 256] : 0.f;       // output_linear's four rows sit where the alpha block is
+    if (st == 8) return r < 256 ? P.p[P_FEAT_B][r] : (r == 256 ? P.p[P_ALPHA_B][0] : 0.f);
+    if (st == 9) return r < 128 ? P.p[P_VIEWS_B][r] : 0.f;
+    return r < 3 ? P.p[P_RGB_B][r] : 0.f;
+}
 __global__ __launch_bounds__(1024) void f16_stage_scale_kernel(nm_mlp_desc d, DevParams P, unsigned* __restrict__ work, float* __restrict__ wscale) {
     const int st = blockIdx.x;
     const StageShape sh = stage_shape(st);
     const int per_row = 2 * sh.steps * 8, total = sh.nblk * 32 * per_row;
-    float mx = 0.f;
+    unsigned mx = 0u;                                                    // bits of the largest magnitude
     for (int i = blockIdx.y * 1024 + threadIdx.x; i < total; i += 1024 * kScaleSlices) {
         const int n = i / per_row, r = i - n * per_row;
-        mx = fmaxf(mx, fabsf(stage_weight(&d, P.p, st, n, r >> 3, r & 7)));
+        mx = max(mx, __float_as_uint(fabsf(stage_weight(&d, P.p, st, n, r >> 3, r & 7))));
     }
-    __shared__ float part[1024];
+    if (blockIdx.y == 0 && (int)threadIdx.x < sh.nblk * 32) {            // a non-finite bias poisons the stage like a weight; a finite one has no say
+        const unsigned b = __float_as_uint(fabsf(stage_bias(P, d.plain_head, st, threadIdx.x)));
+        if (b >= 0x7F800000u) mx = max(mx, b);
+    }
+    __shared__ unsigned part[1024];
     part[threadIdx.x] = mx;
     __syncthreads();
     for (int o = 512; o > 0; o >>= 1) {
-        if (threadIdx.x < o) part[threadIdx.x] = fmaxf(part[threadIdx.x], part[threadIdx.x + o]);
+        if (threadIdx.x < o) part[threadIdx.x] = max(part[threadIdx.x], part[threadIdx.x + o]);
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        atomicMax(&work[st], __float_as_uint(part[0]));                  // (magnitudes: non-negative floats order like their bit patterns; a NaN weight never raised mx)
+        atomicMax(&work[st], part[0]);
         __threadfence();
         if (atomicAdd(&work[kStages + st], 1u) == kScaleSlices - 1) {
-            const float all = __uint_as_float(atomicMax(&work[st], 0u));
+            const unsigned bits = atomicMax(&work[st], 0u);
+            const float all = __uint_as_float(bits);
             int k = 8;
             while (k > -40 && all * ldexpf(1.f, k) > 32000.f) --k;
-            wscale[st] = ldexpf(1.f, k);
+            wscale[st] = bits >= 0x7F800000u ? __uint_as_float(0x7FC00000u) : ldexpf(1.f, k);
         }
     }
 }
@@ -259,19 +311,14 @@ __global__ __launch_bounds__(256) void f16_bias_kernel(DevParams P, const float*
     if (i >= kBiasFloats + kF16TabFloats) return;
     if (i >= kBiasFloats) {                                           // [2^-k (11)] [2^-(k + 5) (11)] [2 spare]
         const int q = i - kBiasFloats;
-        bias[i] = q < kStages ? 1.f / wscale[q] : (q < 2 * kStages ? 1.f / (wscale[q - kStages] * 32.f) : 0.f);
+        float poison = 0.f;                                            // NaN as soon as one stage holds a non-finite parameter (f16_stage_scale_kernel)
+        for (int s = 0; s < kStages; ++s) poison += wscale[s] * 0.f;
+        bias[i] = q < kStages ? 1.f / wscale[q] + poison : (q < 2 * kStages ? 1.f / (wscale[q - kStages] * 32.f) + poison : 0.f);
         return;
     }
     int st = 0;
     while (st + 1 < kStages && i >= stage_b_off(st + 1)) ++st;
-    const int r = i - stage_b_off(st);
-    float v = 0.f;
-    if (st <= 7) v = P.p[P_PTS_W + 2 * st + 1][r];
-    else if (plain_head) v = (st == 8 && r >= 256 && r < 260) ? P.p[P_OUT_B][r - 256] : 0.f;       // output_linear's four rows sit where the alpha block is
-    else if (st == 8) v = r < 256 ? P.p[P_FEAT_B][r] : (r == 256 ? P.p[P_ALPHA_B][0] : 0.f);
-    else if (st == 9) v = r < 128 ? P.p[P_VIEWS_B][r] : 0.f;
-    else v = r < 3 ? P.p[P_RGB_B][r] : 0.f;
-    bias[i] = v * wscale[st] * 32.f;
+    bias[i] = stage_bias(P, plain_head, st, i - stage_b_off(st)) * wscale[st] * 32.f;
 }
 
 // ---- NM_PREC_I8X3 image: [fragments (i8 limb steps, then bf16 PE steps) | pad | units | biases | kappa] ----------------
@@ -283,6 +330,18 @@ __global__ __launch_bounds__(256) void f16_bias_kernel(DevParams P, const float*
 // u_L[n] = q[n] / kappa_L.  Biases and the rows of the encoding (split-bf16) parts are divided by u_L[n] (ReLU commutes
 // with positive scaling).  Stage 0 has u = 1.  sigma (stage 8 row 256) and rgb (stage 10 rows 0..2) are multiplied by
 // their unit at the output.  `units` holds u_L[n] for every stage in the bias table's layout.
+// The bias enters the rule where a unit stands out of its layer.  The next stage requantises every sample's stored row with ONE step, its largest
+// stored value / 32639, so the stored values of a layer have to be of one size.  q[n] from the weights alone assumes that a unit's output is as large
+// as its weights make it; a unit whose incoming weights are small against its bias (a nearly dead unit of a trained net, a pruned or regularised
+// row) then gets a tiny unit, its stored value bias / u is huge, it alone sets the row maximum and every other feature of the sample loses that
+// many bits.  So every row also gets a data-free estimate of its output's size, est[n] = sqrt(b[n]^2 + sum_f (W[n][f] est_in[f])^2) (encoding
+// inputs count as 1; est of one stage is est_in of the next), and where est[n] / q[n] -- the stored size -- exceeds kUnitOutlier times the layer's
+// median of it, q[n] is raised to est[n] / (kUnitOutlier * median): the unit is stored no larger than that above its peers, at the price of weight
+// bits it cannot use (its output is its bias).  A layer whose rows are alike -- torch's initialisation, every net of the suite and of bench.py -- has
+// no such row and its image is byte for byte what the weights-only rule wrote (tests/test_mlp_pack_edges.py).  An all-zero row with a bias is the
+// same case (est = |b|); an all-zero row without one keeps u = 1.
+constexpr float kUnitOutlier = 4.f;
+constexpr float kBalanceFrom = 16.f;    // a next-layer column this far above the median column is balanced (see below in pack_image8)
 constexpr int kKappaFloats = 16;
 static inline int64_t image8_bytes() { return kWeightBytes8 + kWeightPadBytes + (2 * (int64_t)kBiasFloats + kKappaFloats) * 4; }
 
@@ -308,7 +367,8 @@ static void pack_image8(const nm_mlp_desc* d, const float* const* P, uint8_t* im
     float* units = reinterpret_cast<float*>(img + kWeightBytes8 + kWeightPadBytes);
     float* bias = units + kBiasFloats;
     float* kappa = bias + kBiasFloats;
-    std::vector<float> weff(256);
+    const int kpe = 3 + 6 * d->pos_n_freqs, kdpe = 3 + 6 * d->dir_n_freqs;
+    std::vector<double> est_in(288, 0.0), est(288, 0.0);      // size estimates of the previous stage's outputs / of this stage's (true values)
     for (int st = 0; st < kStages; ++st) {
         const StageShape8 sh = stage_shape8(st);
         const int nh = sh.i8steps * 32;                       // hidden input width of the i8 part
@@ -322,6 +382,19 @@ static void pack_image8(const nm_mlp_desc* d, const float* const* P, uint8_t* im
         else memcpy(b, P[P_RGB_B], 3 * 4);
         kappa[st] = 1.f;
         for (int n = 0; n < nrows; ++n) u[n] = 1.f;
+        for (int n = 0; n < nrows; ++n) {                     // est[n]: the bias, the encoding part (stages 0, 5, 9; inputs of size 1), the hidden part
+            double v = (double)b[n] * b[n];
+            const float* pe = nullptr;
+            int npe = 0;
+            if (st == 0) { pe = P[P_PTS_W] + (int64_t)n * kpe; npe = kpe; }
+            else if (st == 5) { pe = P[P_PTS_W + 10] + (int64_t)n * (kpe + 256); npe = kpe; }
+            else if (st == 9 && !d->plain_head) { pe = P[P_VIEWS_W] + (int64_t)n * (256 + kdpe) + 256; npe = kdpe; }
+            for (int f = 0; f < npe; ++f) v += (double)pe[f] * pe[f];
+            int col0 = 0;
+            const float* row = sh.i8steps ? hidden_row(d, P, st, n, &col0) : nullptr;
+            if (row) for (int f = 0; f < nh; ++f) { const double w = (double)row[col0 + f] * est_in[f]; v += w * w; }
+            est[n] = sqrt(v);
+        }
         if (sh.i8steps) {
             // units of this stage's hidden input: the previous stage's (stage 9 reads the 256 feature rows of stage 8)
             const float* uin = units + stage_b_off(st - 1);
@@ -333,8 +406,50 @@ static void pack_image8(const nm_mlp_desc* d, const float* const* P, uint8_t* im
                 float mx = 0.f;
                 if (row) for (int f = 0; f < nh; ++f) mx = fmaxf(mx, fabsf(row[col0 + f] * uin[f]));
                 q[n] = mx / (float)kFixedMax;
-                kap = fmaxf(kap, q[n]);
             }
+            std::vector<double> stored;                       // est / q of the rows that have weights: the size a row is stored at
+            for (int n = 0; n < nrows; ++n) if (q[n] > 0.f) stored.push_back(est[n] / q[n]);
+            if (!stored.empty()) {
+                std::nth_element(stored.begin(), stored.begin() + stored.size() / 2, stored.end());
+                const double cap = (double)kUnitOutlier * stored[stored.size() / 2];
+                for (int n = 0; n < nrows; ++n) {
+                    int col0 = 0;
+                    if (hidden_row(d, P, st, n, &col0) && cap > 0.0 && est[n] > cap * q[n]) q[n] = (float)(est[n] / cap);
+                }
+            }
+            // ... and where one unit's column of the NEXT layer's folded weights W'[m][n] * u[n] stands out: an outlier row here (large q[n]) or an outlier
+            // column there (large c[n] = max_m |W'[m][n]|).  A next-layer row's int16 step is set by its largest folded weight, so a column kBalanceFrom x
+            // the median leaves every other weight of that layer that many bits fewer.  The units below the geometric mean of the largest and the median
+            // column are raised to it (q only ever grows: a raised row gives up bits of its own weights and of its stored value) -- the loss is split
+            // between this layer's weights, its stored activations and the next layer's weights instead of falling on the last alone.
+            const int nxt = st == 10 ? -1 : st + 1, nfeed = st == 9 ? 128 : 256;      // the rows the next stage reads as its hidden input
+            if (nxt > 0 && !(d->plain_head && nxt > 8)) {
+                std::vector<double> c(nfeed, 0.0), g;
+                for (int m = 0; m < stage_shape8(nxt).nblk * 32; ++m) {
+                    int col0 = 0;
+                    const float* row = hidden_row(d, P, nxt, m, &col0);
+                    if (row) for (int n = 0; n < nfeed; ++n) c[n] = fmax(c[n], fabs((double)row[col0 + n]));
+                }
+                for (int n = 0; n < nfeed; ++n) if (q[n] > 0.f && c[n] > 0.0) g.push_back(q[n] * c[n]);
+                if (!g.empty()) {
+                    std::nth_element(g.begin(), g.begin() + g.size() / 2, g.end());
+                    const double med = g[g.size() / 2], top = *std::max_element(g.begin(), g.end());
+                    if (top > (double)kBalanceFrom * med) {
+                        // how much of the gap the other units take: half of it (in bits) where the outlier is a row of THIS layer -- its output is that
+                        // much larger too, and with it the error everything downstream inherits from it; a third where it is a column of the next layer
+                        // and this layer's own outputs are ordinary
+                        std::vector<double> qs;
+                        double qtop = 0.0;
+                        for (int n = 0; n < nfeed; ++n) if (q[n] > 0.f && c[n] > 0.0) { qs.push_back(q[n]); if (q[n] * c[n] == top) qtop = q[n]; }
+                        std::nth_element(qs.begin(), qs.begin() + qs.size() / 2, qs.end());
+                        const bool row_outlier = qtop > (double)kBalanceFrom * qs[qs.size() / 2];
+                        const double floor_g = row_outlier ? sqrt(top * med) : cbrt(top * med * med);
+                        for (int n = 0; n < nfeed; ++n)
+                            if (q[n] > 0.f && c[n] > 0.0 && q[n] * c[n] < floor_g) q[n] = (float)(floor_g / c[n]);
+                    }
+                }
+            }
+            for (int n = 0; n < nrows; ++n) kap = fmaxf(kap, q[n]);
             if (!(kap > 0.f)) kap = 1.f;
             kappa[st] = kap;
             for (int n = 0; n < nrows; ++n) {
@@ -365,6 +480,7 @@ static void pack_image8(const nm_mlp_desc* d, const float* const* P, uint8_t* im
                 }
         }
         for (int n = 0; n < nrows; ++n) b[n] /= u[n];
+        est_in.swap(est);
         // ---- split-bf16 encoding steps: the bf16 image's values for these k-slots, in this stage's output units
         for (int nb = 0; nb < sh.nblk; ++nb)
             for (int t = 0; t < sh.bfsteps; ++t) {
@@ -512,6 +628,7 @@ int nm_mlp_pack(const nm_mlp_desc* desc, const float* const* host_params, void* 
     if (int e = nm::validate_desc(desc)) return e;
     NM_REQUIRE(host_params && host_out, "nm_mlp_pack: null pointer");
     for (int i = 0; i < (desc->plain_head ? 18 : 24); ++i) NM_REQUIRE(host_params[i], "nm_mlp_pack: host_params[%d] is null", i);
+    if (int e = nm::check_finite("nm_mlp_pack", desc, host_params)) return e;
     nm::pack_image(desc, host_params, static_cast<uint8_t*>(host_out));
     return NM_OK;
 }
@@ -520,6 +637,7 @@ int nm_mlp_pack_f16(const nm_mlp_desc* desc, const float* const* host_params, vo
     if (int e = nm::validate_desc(desc)) return e;
     NM_REQUIRE(host_params && host_out, "nm_mlp_pack_f16: null pointer");
     for (int i = 0; i < (desc->plain_head ? 18 : 24); ++i) NM_REQUIRE(host_params[i], "nm_mlp_pack_f16: host_params[%d] is null", i);
+    if (int e = nm::check_finite("nm_mlp_pack_f16", desc, host_params)) return e;
     nm::pack_image(desc, host_params, static_cast<uint8_t*>(host_out), true);
     return NM_OK;
 }
@@ -533,6 +651,7 @@ int nm_mlp_pack_i8(const nm_mlp_desc* desc, const float* const* host_params, voi
     if (int e = nm::validate_desc(desc)) return e;
     NM_REQUIRE(host_params && host_out, "nm_mlp_pack_i8: null pointer");
     for (int i = 0; i < (desc->plain_head ? 18 : 24); ++i) NM_REQUIRE(host_params[i], "nm_mlp_pack_i8: host_params[%d] is null", i);
+    if (int e = nm::check_finite("nm_mlp_pack_i8", desc, host_params)) return e;
     nm::pack_image8(desc, host_params, static_cast<uint8_t*>(host_out));
     return NM_OK;
 }
@@ -546,6 +665,7 @@ int nm_mlp_pack_i8s(const nm_mlp_desc* desc, const float* const* host_params, vo
     if (int e = nm::validate_desc(desc)) return e;
     NM_REQUIRE(host_params && host_out, "nm_mlp_pack_i8s: null pointer");
     for (int i = 0; i < (desc->plain_head ? 18 : 24); ++i) NM_REQUIRE(host_params[i], "nm_mlp_pack_i8s: host_params[%d] is null", i);
+    if (int e = nm::check_finite("nm_mlp_pack_i8s", desc, host_params)) return e;
     std::vector<uint8_t> img8((size_t)nm::image8_bytes());
     nm::pack_image8(desc, host_params, img8.data());
     nm::pack_stream8s(img8.data(), static_cast<uint8_t*>(host_out), desc->plain_head != 0);
@@ -558,6 +678,7 @@ int nm_mlp_create(const nm_mlp_desc* desc, const float* const* host_params, cons
     NM_REQUIRE(host_params && host_pos_tab && host_dir_tab && out, "nm_mlp_create: null pointer");
     const int plain = desc->plain_head;
     for (int i = 0; i < (plain ? 18 : 24); ++i) NM_REQUIRE(host_params[i], "nm_mlp_create: host_params[%d] is null", i);
+    if (int e = nm::check_finite("nm_mlp_create", desc, host_params)) return e;
     const int64_t bytes = nm_mlp_pack_bytes(desc);
     std::vector<uint8_t> img((size_t)bytes);
     nm::pack_image(desc, host_params, img.data());

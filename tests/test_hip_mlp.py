@@ -1,9 +1,15 @@
 """-m gpu: the fused PE + MLP kernel (MFMA split-bf16 and exact-f32 modes) vs the CPU oracle, layer by layer."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import nerf_mlp
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+from mlp_edges import f64_network  # noqa: E402,F401  (the float64 network the tests below are judged against)
 
 pytestmark = pytest.mark.gpu
 
@@ -227,21 +233,6 @@ def test_sigma_only_is_bit_identical(gpu_nets, prec, R, S):
         assert (dens[..., :3] == 0).all()
     else:
         assert torch.equal(dens, full)
-
-
-def f64_network(sd, spec, pts, dirs):
-    sd64 = {k: v.astype(np.float64) for k, v in sd.items()}
-    x_pe = nerf_mlp.embed(pts, spec.mapping, *spec.pos).astype(np.float64)
-    d_pe = nerf_mlp.embed(dirs, spec.mapping, *spec.dir).astype(np.float64)
-    lin = lambda h, n: h @ sd64[f'nerf.{n}.weight'].T + sd64[f'nerf.{n}.bias']      # noqa: E731
-    h = x_pe
-    for i in range(8):
-        h = np.maximum(lin(h, f'pts_linears.{i}'), 0)
-        if i == 4:
-            h = np.concatenate([x_pe, h], -1)
-    sigma = lin(h, 'alpha_linear')[:, 0]
-    rgb = lin(np.maximum(lin(np.concatenate([lin(h, 'feature_linear'), d_pe], -1), 'views_linears.0'), 0), 'rgb_linear')
-    return rgb, sigma
 
 
 def test_fp16x3_is_float32_class(gpu_nets):
