@@ -152,6 +152,12 @@ int nm_mlp_pack_i8(const nm_mlp_desc* desc, const float* const* host_params, voi
  * stage 8 with the alpha block first; stage 9; stage 10 -- followed by 8 KB of zeros (the ring copies whole 1 KB pieces: a 10-step block is rounded up). */
 int64_t nm_mlp_pack_i8s_bytes(const nm_mlp_desc* desc);
 int nm_mlp_pack_i8s(const nm_mlp_desc* desc, const float* const* host_params, void* host_out);
+/* host-only: the two cuts of that stream that nm_mlp_forward_rays_live's launches walk (not the plain-head net).  Trunk: steps [0, 520) -- through the
+ * alpha block -- then the next tile's first two ring blocks, 4 steps each padded with zeros to 8 (the ring looks two blocks ahead), then 8 KB of zeros.
+ * Head: steps [520, 628), then 8 KB of zeros. */
+int64_t nm_mlp_pack_i8s_trunk_bytes(const nm_mlp_desc* desc);
+int64_t nm_mlp_pack_i8s_head_bytes(const nm_mlp_desc* desc);
+int nm_mlp_pack_i8s_live(const nm_mlp_desc* desc, const float* const* host_params, void* host_trunk_out, void* host_head_out);
 int nm_mlp_create(const nm_mlp_desc* desc, const float* const* host_params, const float* host_pos_tab,
                   const float* host_dir_tab, nm_mlp_t* out);
 int nm_mlp_destroy(nm_mlp_t mlp);
@@ -231,6 +237,18 @@ int nm_mlp_backward_net16(nm_mlp_t mlp, const float* const* dev_params, const fl
  * with view direction direction[r] (ray_utils.py:131-132); out [R,S,4]. */
 int nm_mlp_forward_rays(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals,
                         int64_t R, int S, int precision, float sigma_scale, float* out, nm_stream_t stream);
+/* nm_mlp_forward_rays for a pass whose output is composited and nothing else (raw2outputs: alpha = 1 - exp(-relu(sigma) dist)): a sample whose
+ * stored density sigma * sigma_scale is <= 0 has weight exactly 0, so its colour is never seen -- it is returned as (0, 0, 0) and the colour head
+ * (feature_linear, views_linears, rgb_linear: 17 % of the MACs) is evaluated on the other samples only.  Their records, and every density, are
+ * BIT-IDENTICAL to nm_mlp_forward_rays'; all records are finite.  NM_PREC_I8X3 with the view-dependent head; any other precision, the plain-head
+ * net and NEUMAN_I8_KERNEL=w run nm_mlp_forward_rays itself.  The rays are walked in chunks of chunk_samples samples (whole rays; <= 0:
+ * NM_LIVE_CHUNK_SAMPLES); per chunk a counter reset, a trunk launch that lists the live samples with their activations (520 B each) in
+ * `workspace`, and a head launch sized on the device from that list -- no host synchronisation.  workspace (16-byte aligned):
+ * nm_mlp_forward_rays_live_workspace_bytes(R, S, chunk_samples) bytes = one chunk with every sample live. */
+#define NM_LIVE_CHUNK_SAMPLES (1 << 21)
+int64_t nm_mlp_forward_rays_live_workspace_bytes(int64_t R, int S, int64_t chunk_samples);
+int nm_mlp_forward_rays_live(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S, int precision,
+                             float sigma_scale, float* out, void* workspace, int64_t workspace_bytes, int64_t chunk_samples, nm_stream_t stream);
 /* Density only, for a pass whose colours the caller discards -- the coarse pass of a two-pass render: the reference
  * composites it (render_utils.py:139) and keeps nothing but the weights that place the importance samples (:141), which
  * depend on sigma alone.  Same arguments as nm_mlp_forward_rays; out [R,S,4] receives (0, 0, 0, sigma * sigma_scale) with

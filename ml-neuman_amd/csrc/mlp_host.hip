@@ -530,6 +530,20 @@ static void pack_stream8s(const uint8_t* img8, uint8_t* out, bool plain = false)
     put(10, 0, 0, 4);
     if (dst - out != kWeightBytes8) abort();
 }
+// the two cuts of that stream behind nm_mlp_forward_rays_live (never the plain-head net's): the trunk launch's = blocks 0..68 and the look-ahead
+// padding, which is pack_stream8s' plain form of the whole net's image (the alpha block holds the alpha row); the head launch's = blocks 69..81 = steps
+// [520, 628) of the whole stream, walked round and round (the ring's rounded-up copy of a 10-step block never passes the 4-step block that ends it)
+constexpr int64_t kTrunkSteps8 = 8 * 4 + 7 * 8 * 8 + 8 * 4 + 8, kHeadSteps8 = 8 * 8 + 4 * 10 + 4;
+static_assert((kTrunkSteps8 + kHeadSteps8) * kStepBytes == kWeightBytes8 && (kTrunkSteps8 + 16) * kStepBytes == kPlainStreamBytes8, "stream cuts");
+constexpr int64_t kTrunkStreamBytes8 = kPlainStreamBytes8 + kWeightPadBytes, kHeadStreamBytes8 = kHeadSteps8 * kStepBytes + kWeightPadBytes;
+static void pack_stream8s_live(const uint8_t* img8, uint8_t* trunk, uint8_t* head) {
+    std::vector<uint8_t> whole((size_t)(kWeightBytes8 + kWeightPadBytes)), cut(whole.size());
+    pack_stream8s(img8, whole.data());
+    pack_stream8s(img8, cut.data(), true);
+    memcpy(trunk, cut.data(), (size_t)kTrunkStreamBytes8);
+    memset(head, 0, (size_t)kHeadStreamBytes8);
+    memcpy(head, whole.data() + kTrunkSteps8 * kStepBytes, (size_t)(kHeadSteps8 * kStepBytes));
+}
 
 // ---- the density-only fp16x3 activation-stationary kernel's stream (mlp_f16t.hip): the k-steps of stages 0..7 and of the alpha block of the
 // fp16 image (frag_off) in the order the kernel consumes them -- output blocks in PAIRS (two accumulator chains), a ring unit = 8 steps of
@@ -598,6 +612,7 @@ struct nm_mlp_s {
     float* d_consts8;      // NM_PREC_I8X3: units | biases | kappa (the tail of the nm_mlp_pack_i8 image)
     uint8_t* d_stream8;    // NM_PREC_I8X3: the image's fragments as per-wave streams (nerf_mlp_i8w_kernel)
     uint8_t* d_image8;     // NM_PREC_I8X3: the workgroup stream of nerf_mlp_i8s_kernel (pack_stream8s), fragments + prefetch pad
+    uint8_t* d_trunk8;     //   and its two cuts for nm_mlp_forward_rays_live (pack_stream8s_live): trunk launch | head launch in one allocation
     uint8_t* d_stream16t;  // NM_PREC_FP16X3, density only: the stream of nerf_sigma_f16t_kernel (sigma_stream_kernel over d_image16)
     int* d_sigma_tab;      //   its piece table
     uint8_t* d_bwd_image;  // the transposed hidden weights of the backward-data chain (mlp_bwd.hip), repacked from live parameters per call
@@ -672,6 +687,28 @@ int nm_mlp_pack_i8s(const nm_mlp_desc* desc, const float* const* host_params, vo
     return NM_OK;
 }
 
+int64_t nm_mlp_pack_i8s_trunk_bytes(const nm_mlp_desc* desc) {
+    if (nm::validate_desc(desc) != NM_OK || desc->plain_head) return -1;
+    return nm::kTrunkStreamBytes8;
+}
+
+int64_t nm_mlp_pack_i8s_head_bytes(const nm_mlp_desc* desc) {
+    if (nm::validate_desc(desc) != NM_OK || desc->plain_head) return -1;
+    return nm::kHeadStreamBytes8;
+}
+
+int nm_mlp_pack_i8s_live(const nm_mlp_desc* desc, const float* const* host_params, void* host_trunk_out, void* host_head_out) {
+    if (int e = nm::validate_desc(desc)) return e;
+    NM_REQUIRE(!desc->plain_head, "nm_mlp_pack_i8s_live: the plain-head net has no colour head to split off");
+    NM_REQUIRE(host_params && host_trunk_out && host_head_out, "nm_mlp_pack_i8s_live: null pointer");
+    for (int i = 0; i < 24; ++i) NM_REQUIRE(host_params[i], "nm_mlp_pack_i8s_live: host_params[%d] is null", i);
+    if (int e = nm::check_finite("nm_mlp_pack_i8s_live", desc, host_params)) return e;
+    std::vector<uint8_t> img8((size_t)nm::image8_bytes());
+    nm::pack_image8(desc, host_params, img8.data());
+    nm::pack_stream8s_live(img8.data(), static_cast<uint8_t*>(host_trunk_out), static_cast<uint8_t*>(host_head_out));
+    return NM_OK;
+}
+
 int nm_mlp_create(const nm_mlp_desc* desc, const float* const* host_params, const float* host_pos_tab,
                   const float* host_dir_tab, nm_mlp_t* out) {
     if (int e = nm::validate_desc(desc)) return e;
@@ -690,6 +727,8 @@ int nm_mlp_create(const nm_mlp_desc* desc, const float* const* host_params, cons
     nm::pack_image8(desc, host_params, img8.data());            // (the plain-head net: output_linear's rows in the alpha block, stages 9 / 10 zero;
     nm::pack_stream8(img8.data(), str8.data());                 //  only the activation-stationary kernel has its form)
     nm::pack_stream8s(img8.data(), str8s.data(), plain != 0);
+    std::vector<uint8_t> live8(plain ? 0 : (size_t)(nm::kTrunkStreamBytes8 + nm::kHeadStreamBytes8));
+    if (!plain) nm::pack_stream8s_live(img8.data(), live8.data(), live8.data() + nm::kTrunkStreamBytes8);
 
     // reference-layout image for the exact-f32 kernel
     const int kpe = 3 + 6 * desc->pos_n_freqs, kdpe = 3 + 6 * desc->dir_n_freqs;
@@ -729,7 +768,7 @@ int nm_mlp_create(const nm_mlp_desc* desc, const float* const* host_params, cons
     m->pos_octaves = octaves(tab, desc->pos_n_freqs);
     m->dir_octaves = octaves(tab + 96, desc->dir_n_freqs);
 
-    m->d_image = nullptr; m->d_image16 = nullptr; m->d_consts8 = nullptr; m->d_stream8 = nullptr; m->d_image8 = nullptr; m->d_stream16t = nullptr; m->d_sigma_tab = nullptr; m->d_bwd_image = nullptr; m->d_petab = nullptr; m->d_ref = nullptr; m->d_wscale16 = nullptr;
+    m->d_image = nullptr; m->d_image16 = nullptr; m->d_consts8 = nullptr; m->d_stream8 = nullptr; m->d_image8 = nullptr; m->d_trunk8 = nullptr; m->d_stream16t = nullptr; m->d_sigma_tab = nullptr; m->d_bwd_image = nullptr; m->d_petab = nullptr; m->d_ref = nullptr; m->d_wscale16 = nullptr;
     int rc = nm::check_hip(hipMalloc(&m->d_image, (size_t)bytes), "nm_mlp_create: hipMalloc(image)");
     const size_t consts_off = (size_t)(nm::kWeightBytes8 + nm::kWeightPadBytes), consts_bytes = img8.size() - consts_off;
     if (!rc) rc = nm::check_hip(hipMalloc(&m->d_consts8, consts_bytes), "nm_mlp_create: hipMalloc(consts8)");
@@ -738,6 +777,8 @@ int nm_mlp_create(const nm_mlp_desc* desc, const float* const* host_params, cons
     if (!rc) rc = nm::check_hip(hipMemcpy(m->d_stream8, str8.data(), str8.size(), hipMemcpyHostToDevice), "nm_mlp_create: upload stream8");
     if (!rc) rc = nm::check_hip(hipMalloc(&m->d_image8, consts_off), "nm_mlp_create: hipMalloc(image8)");
     if (!rc) rc = nm::check_hip(hipMemcpy(m->d_image8, str8s.data(), consts_off, hipMemcpyHostToDevice), "nm_mlp_create: upload image8");
+    if (!rc && !plain) rc = nm::check_hip(hipMalloc(&m->d_trunk8, live8.size()), "nm_mlp_create: hipMalloc(trunk8)");
+    if (!rc && !plain) rc = nm::check_hip(hipMemcpy(m->d_trunk8, live8.data(), live8.size(), hipMemcpyHostToDevice), "nm_mlp_create: upload trunk8");
     if (!rc) rc = nm::check_hip(hipMalloc(&m->d_petab, sizeof(tab)), "nm_mlp_create: hipMalloc(petab)");
     if (!rc) rc = nm::check_hip(hipMalloc(&m->d_ref, ref.size() * 4), "nm_mlp_create: hipMalloc(ref)");
     if (!rc) rc = nm::check_hip(hipMemcpy(m->d_image, img.data(), (size_t)bytes, hipMemcpyHostToDevice), "nm_mlp_create: upload image");
@@ -798,6 +839,7 @@ int nm_mlp_destroy(nm_mlp_t m) {
     if (m->d_consts8) (void)hipFree(m->d_consts8);
     if (m->d_stream8) (void)hipFree(m->d_stream8);
     if (m->d_image8) (void)hipFree(m->d_image8);
+    if (m->d_trunk8) (void)hipFree(m->d_trunk8);
     if (m->d_stream16t) (void)hipFree(m->d_stream16t);
     if (m->d_sigma_tab) (void)hipFree(m->d_sigma_tab);
     if (m->d_bwd_image) (void)hipFree(m->d_bwd_image);
@@ -806,6 +848,13 @@ int nm_mlp_destroy(nm_mlp_t m) {
     if (m->d_wscale16) (void)hipFree(m->d_wscale16);
     delete m;
     return NM_OK;
+}
+
+// NM_PREC_I8X3, whole network, all four outputs: the activation-stationary kernel (mlp_i8s.hip) -- bit-identical to the wave-specialised
+// one of mlp.hip, which keeps the stage-by-stage / profiling / density-only forms (and everything under NEUMAN_I8_KERNEL=w or =r)
+static bool i8_as_kernel() {
+    static const bool on = [] { const char* e = getenv("NEUMAN_I8_KERNEL"); return !e || !strcmp(e, "as"); }();
+    return on;
 }
 
 static int mlp_dispatch(nm_mlp_t m, const float* pts, const float* dirs, const float* origin, const float* direction,
@@ -842,9 +891,7 @@ static int mlp_dispatch(nm_mlp_t m, const float* pts, const float* dirs, const f
     L.plain_head = m->desc.plain_head;
     L.wstream8 = m->d_stream8;
     L.consts8 = m->d_consts8;
-    // NM_PREC_I8X3, whole network, all four outputs: the activation-stationary kernel (mlp_i8s.hip) -- bit-identical to the wave-specialised
-    // one of mlp.hip, which keeps the stage-by-stage / profiling / density-only forms (and everything under NEUMAN_I8_KERNEL=w or =r)
-    static const bool i8_as = [] { const char* e = getenv("NEUMAN_I8_KERNEL"); return !e || !strcmp(e, "as"); }();
+    const bool i8_as = i8_as_kernel();
     // NM_PREC_FP16X3, density only (the sampling pass of a two-pass render): the activation-stationary kernel of mlp_f16t.hip -- bit-identical
     // sigma; NEUMAN_SIGMA_KERNEL=w keeps nerf_mlp_kernel for it
     const char* sk = getenv("NEUMAN_SIGMA_KERNEL");              // (read per call: the parity tests switch it inside one process)
@@ -1027,6 +1074,61 @@ int nm_mlp_forward_rays(nm_mlp_t mlp, const float* origin, const float* directio
     NM_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "nm_mlp_forward_rays: out must be 16-byte aligned");
     return mlp_dispatch(mlp, nullptr, nullptr, origin, direction, z_vals, R * (int64_t)S, S, 1, precision, -2, sigma_scale, out,
                         nullptr, stream);
+}
+
+// ---- the shading pass whose output is composited and nothing else: colour head on live samples only (mlp_i8s.hip TRUNK + mlp_i8h.hip)
+static int64_t live_chunk_rays(int64_t R, int S, int64_t chunk_samples) {              // a chunk is whole rays
+    if (chunk_samples <= 0) chunk_samples = NM_LIVE_CHUNK_SAMPLES;
+    const int64_t rays = chunk_samples / S;
+    return rays < 1 ? 1 : rays > R ? R : rays;
+}
+static int64_t live_cap(int64_t R, int S, int64_t chunk_samples) {                     // list entries of one chunk, every sample live
+    return (live_chunk_rays(R, S, chunk_samples) * S + 255) / 256 * 256;
+}
+
+int64_t nm_mlp_forward_rays_live_workspace_bytes(int64_t R, int S, int64_t chunk_samples) {
+    if (R < 0 || S < 1) return -1;
+    return live_cap(R, S, chunk_samples) * (512 + 4 + 4) + 256;
+}
+
+int nm_mlp_forward_rays_live(nm_mlp_t m, const float* origin, const float* direction, const float* z_vals, int64_t R, int S, int precision,
+                             float sigma_scale, float* out, void* workspace, int64_t workspace_bytes, int64_t chunk_samples, nm_stream_t stream) {
+    NM_REQUIRE(m, "nm_mlp_forward_rays_live: null handle");
+    if (m->desc.plain_head || precision != NM_PREC_I8X3 || !i8_as_kernel())            // nothing to split off / another kernel's arithmetic
+        return nm_mlp_forward_rays(m, origin, direction, z_vals, R, S, precision, sigma_scale, out, stream);
+    NM_REQUIRE(R == 0 || (origin && direction && z_vals && out && workspace), "nm_mlp_forward_rays_live: null pointer");
+    NM_REQUIRE(R >= 0 && S >= 1, "nm_mlp_forward_rays_live: bad sizes");
+    NM_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0, "nm_mlp_forward_rays_live: out and workspace must be 16-byte aligned");
+    NM_REQUIRE(workspace_bytes >= nm_mlp_forward_rays_live_workspace_bytes(R, S, chunk_samples), "nm_mlp_forward_rays_live: workspace of %lld bytes, %lld needed",
+               (long long)workspace_bytes, (long long)nm_mlp_forward_rays_live_workspace_bytes(R, S, chunk_samples));
+    if (R == 0) return NM_OK;
+    const int64_t cap = live_cap(R, S, chunk_samples), rays = live_chunk_rays(R, S, chunk_samples);
+    NM_REQUIRE(rays * S < (1ll << 31), "nm_mlp_forward_rays_live: a chunk of %lld samples", (long long)(rays * S));
+    nm::MlpLaunch L;
+    L.wpack = nullptr; L.bias = nullptr; L.wpack16 = nullptr; L.bias16 = nullptr; L.wstream8 = nullptr;
+    L.petab = m->d_petab;
+    L.pe_kind = m->desc.pe_kind; L.pos_nfreq = m->desc.pos_n_freqs; L.dir_nfreq = m->desc.dir_n_freqs;
+    L.pos_octaves = m->pos_octaves; L.dir_octaves = m->dir_octaves;
+    L.plain_head = 0;
+    L.consts8 = m->d_consts8;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    nm::LiveList live;
+    live.x = reinterpret_cast<uint4*>(ws);
+    live.sx = reinterpret_cast<float*>(ws + cap * 512);
+    live.idx = reinterpret_cast<int*>(ws + cap * 516);
+    live.count = reinterpret_cast<int*>(ws + cap * 520);
+    live.cap = cap;
+    hipStream_t st = nm::as_stream(stream);
+    for (int64_t r0 = 0; r0 < R; r0 += rays) {                                          // per chunk: counter reset, trunk launch, head launch
+        const int64_t nr = R - r0 < rays ? R - r0 : rays;
+        if (int rc = nm::check_hip(hipMemsetAsync(live.count, 0, 4, st), "nm_mlp_forward_rays_live: counter reset")) return rc;
+        float* o = out + r0 * S * 4;
+        if (int rc = nm::launch_mlp_i8s(L, m->d_trunk8, nullptr, nullptr, origin + r0 * 3, direction + r0 * 3, z_vals + r0 * S, nr * S, S, 1, sigma_scale, o, st,
+                                        nullptr, &live))
+            return rc;
+        if (int rc = nm::launch_mlp_i8h(L, m->d_trunk8 + nm::kTrunkStreamBytes8, direction + r0 * 3, S, live, nr * S, o, st)) return rc;
+    }
+    return NM_OK;
 }
 
 int nm_mlp_sigma_rays(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S,

@@ -21,17 +21,6 @@
 
 namespace {
 
-constexpr int kWaves = 8;                        // 8 waves x 32 samples = 256 samples per workgroup, one workgroup per CU
-constexpr int kTile = kWaves * kRows;
-// LDS: the encodings of each wave's 32 rows, wave-private: [wave][8 chunks][hi: 32 rows | lo: 32 rows][16 B] = 8 KB per wave
-constexpr int kPWaveU4 = nm::kPeChunks * 2 * kRows;          // 512 uint4
-constexpr int kPeU4 = kWaves * kPWaveU4;
-// the weight ring: kSlots slots of one ring block (at most 10 k-steps of 2 KB; sized for 12)
-constexpr int kStepU4 = nm::kStepBytes / 16;
-constexpr int kSlotU4 = 12 * kStepU4;
-constexpr int kSlots = 3;                                    // the block being multiplied + two being copied
-constexpr int kBiasU4 = (nm::kBiasFloats + 16 + 3) / 4;      // the bias table and kappa, resident in LDS (a global load per block would sit in the same
-                                                             // in-order VMEM queue as the copies and force them to land early)
 // flat RING block index of a tile (what one barrier hands over): stage 0: 0-7 (4 steps) | 1-4: 8-39 | 5: 40-47 and its encoding part
 // 48-51 (two output blocks x 4 steps each) | 6, 7: 52-67 | 8: 68-76 | 9: 77-80 (10 steps) | 10: 81 (4 steps)
 constexpr int kTileBlocks = 82;
@@ -39,108 +28,12 @@ __host__ __device__ constexpr int block_steps(int i) {
     i = i >= kTileBlocks ? i - kTileBlocks : i;
     return i < 8 ? 4 : i < 77 ? 8 : i < 81 ? 10 : 4;
 }
-__host__ __device__ constexpr int block_pieces(int nsteps) { return (2 * nsteps + kWaves - 1) / kWaves; }   // 1 KB pieces per wave
-
-// ---- the weight ring.  Producer side: every wave copies its share (1 KB pieces i = w, w + 8, ..) of the block TWO ahead; consumer side:
-// all waves read every fragment of the current block.  Hand-over, once per block: each wave waits until its own pieces of the block it is
-// about to enter have landed (counted vmcnt: the pieces of the block after it stay in flight -- issue to landing is about 1 us, longer
-// than a block), then the barrier makes everybody's pieces visible and proves that nobody still reads the slot that is refilled next.
-// The only other VMEM operations of the kernel are the sample loads at the top of a tile and the 16-byte store at its end (the compiler
-// waits vmcnt(0) for the former: two copies land early, once per tile).
-struct Ring {
-    const char* src;           // image + lane * 16 + w * 1024
-    const uint4* rd;           // ring + lane
-    unsigned lds0;             // LDS byte address of slot 0 + w * 1024
-    int off;                   // image offset of the block to copy next
-    int slot;                  // slot of the block to enter next
-    int refill, np, nsteps2;   // the copy in progress: slot, pieces per wave, k-steps of the block
+struct TileStream {                                          // what the ring walks: the whole tile, then the next one
+    static __host__ __device__ constexpr int steps(int i) { return block_steps(i); }
+    static constexpr int kBytes = (int)nm::kWeightBytes8;
 };
-// this wave's piece j of the block at R.off -> slot (a 10-step block is padded to 3 pieces: the excess lands in the unused tail of the slot)
-__device__ __forceinline__ void ring_piece(const Ring& R, int off, int slot, int j) {
-    glds16(R.src + off + j * (kWaves * 1024), __builtin_amdgcn_readfirstlane(R.lds0 + slot * (kSlotU4 * 16) + j * (kWaves * 1024)));
-}
-__device__ __forceinline__ void ring_advance(Ring& R, int nsteps) {
-    R.off += nsteps * nm::kStepBytes;
-    if (R.off == (int)nm::kWeightBytes8) R.off = 0;
-}
-// enter flat block i of the tile; returns this lane's view of block i.  The copy of block i + 2 (into the slot block i - 1 has just given
-// up) is issued from inside the k-loop (ring_copy after k-steps 0, 2, 4): the texture path takes one 1 KB piece at a time, and eight
-// waves issuing theirs right after the barrier would all start their MFMAs late.
-__device__ __forceinline__ const uint4* ring_enter(Ring& R, int i) {
-    const int np1 = block_pieces(block_steps(i + 1));
-    if (np1 == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-    else if (np1 == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    const uint4* cur = R.rd + R.slot * kSlotU4;
-    R.refill = R.slot == 0 ? kSlots - 1 : R.slot - 1;                  // the slot of block i - 1 = of block i + 2
-    R.slot = R.slot == kSlots - 1 ? 0 : R.slot + 1;
-    R.np = block_pieces(block_steps(i + 2));
-    R.nsteps2 = block_steps(i + 2);
-    return cur;
-}
-__device__ __forceinline__ void ring_copy(Ring& R, int j) {
-    if (j < R.np) ring_piece(R, R.off, R.refill, j);
-    if (j == R.np - 1) ring_advance(R, R.nsteps2);
-}
-struct W8 {
-    uint4 h, l;
-};
+typedef RingT<TileStream> Ring;
 
-// NSTEPS limb k-steps of one output block: t = 256 * sum(hi.hi) + sum(hi.lo + lo.hi), exact, in two int32 accumulators (two dependency
-// chains; every weight fragment read from LDS once).  Between the k-steps rides the dequantisation of the PREVIOUS block (PEND), two
-// values per step: in lock-step with its SIMD partner a wave would otherwise do it while nobody uses the matrix pipe.
-// PEND: fp = the previous block's outputs (written here, two per MFMA of the first pass), tp = its accumulators, bias_blk = its biases
-// (this lane's half of every group of 8), m = the running row maximum
-template <int NSTEPS, bool PEND, bool RELU = true>
-__device__ __forceinline__ void k_i8_impl(i32x16& t, const X8& X, const uint4* ws, Ring& R, f32x16& fp, const i32x16& tp, lds_cfloat* bias_blk,
-                                          float sx256, float& m) {
-    i32x16 ah, ac;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { ah[r] = 0; ac[r] = 0; }
-    W8 w[2];
-    w[0].h = ws[0]; w[0].l = ws[64];
-    w[1].h = ws[kStepU4]; w[1].l = ws[kStepU4 + 64];
-#pragma unroll
-    for (int s = 0; s < NSTEPS; ++s) {
-        const uint4 wh = w[s & 1].h, wl = w[s & 1].l;
-        ac = __builtin_amdgcn_mfma_i32_32x32x32_i8(as_i32x4(wh), as_i32x4(X.l[s]), ac, 0, 0, 0);
-        ah = __builtin_amdgcn_mfma_i32_32x32x32_i8(as_i32x4(wh), as_i32x4(X.h[s]), ah, 0, 0, 0);      // (between the two links of the cross-term
-        ac = __builtin_amdgcn_mfma_i32_32x32x32_i8(as_i32x4(wl), as_i32x4(X.h[s]), ac, 0, 0, 0);      // chain: -2.5 % at steady state)
-        if (s + 2 < NSTEPS) { w[s & 1].h = ws[(s + 2) * kStepU4]; w[s & 1].l = ws[(s + 2) * kStepU4 + 64]; }
-        if (s == 0 || s == 2 || s == 4) ring_copy(R, s >> 1);
-        if (PEND) {
-            const int r = 2 * s;
-            const float b0 = bias_blk[8 * (r >> 2) + (r & 3)], b1 = bias_blk[8 * (r >> 2) + (r & 3) + 1];
-            const float f0 = fmaf((float)tp[r], sx256, b0), f1 = fmaf((float)tp[r + 1], sx256, b1);
-            fp[r] = f0;
-            fp[r + 1] = f1;
-            m = RELU ? fmaxf(m, fmaxf(f0, f1)) : fmaxf(m, fmaxf(fabsf(f0), fabsf(f1)));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t[r] = (ah[r] << 8) + ac[r];
-}
-template <int NSTEPS>
-__device__ __forceinline__ void k_i8(i32x16& t, const X8& X, const uint4* ws, Ring& R) {
-    f32x16 nf;
-    float nm_ = 0.f;
-    k_i8_impl<NSTEPS, false>(t, X, ws, R, nf, t, nullptr, 0.f, nm_);
-}
-// NSTEPS split-bf16 k-steps over the wave's encoding rows (chunks c0 ..), accumulated into f
-template <int NSTEPS, bool COPY = false>
-__device__ __forceinline__ void k_bf(f32x16& f, const uint4* pw, int g, int s, const uint4* ws, Ring* R = nullptr, int j0 = 0) {
-#pragma unroll
-    for (int t = 0; t < NSTEPS; ++t) {
-        if (COPY && (t == 1 || t == 3)) ring_copy(*R, j0 + (t >> 1));
-        const uint4 wh = ws[t * kStepU4], wl = ws[t * kStepU4 + 64];
-        const uint4 xh = pw[(2 * t + g) * (2 * kRows) + s], xl = pw[(2 * t + g) * (2 * kRows) + kRows + s];
-        f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wh), as_bf16x8(xl), f, 0, 0, 0);
-        f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wl), as_bf16x8(xh), f, 0, 0, 0);
-        f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wh), as_bf16x8(xh), f, 0, 0, 0);
-    }
-}
 // PLAIN: the use_viewdirs=False net (--specular_can no; models/vanilla.py:116-117, 145): stages 0..7, then ring block 68 holds output_linear's four rows
 // (r, g, b, sigma) where the alpha row is otherwise, and the tile ends there.  The instantiation differs from the default one by ONE wave-uniform exit
 // (and the direction encodings it does not compute) and nothing else: this kernel sits at exactly 256 registers, and every other way of telling the
@@ -148,9 +41,16 @@ __device__ __forceinline__ void k_bf(f32x16& f, const uint4* pw, int g, int s, c
 // stays the default one's, and the STREAM is cut to fit it (mlp_host.hip pack_stream8s): where the look-ahead expects blocks 69 and 70 (8 steps each)
 // it finds the next tile's blocks 0 and 1 (4 steps each, padded to 8), and the exit points the ring at block 2.  The exit tests a.sigma_only == 2 (set by
 // the launch) rather than PLAIN alone, so that the code after it stays in the instantiation: without it the allocation of the stage loop changes too.
+// TRUNK: the first of the two launches that shade live samples only (mlp_i8h.hip is the second; nm_mlp_forward_rays_live): the same exit after block 68 on
+// the whole net's stream cut the same way.  It writes (0, 0, 0, sigma) and, for every sample whose stored density is not <= 0 -- the only ones whose colour
+// compositing can see: alpha = 1 - exp(-relu(sigma) dist) is exactly 0 otherwise -- appends what the colour head needs to a global list: the stage-7
+// activations it holds (X: 512 B), their row scale and the sample's index.  One ballot, one prefix count and one atomic add per wave; the list is
+// [piece 2 t + limb][lane half g][entry][16 B], so that the head's wave loads 32 consecutive entries of a piece as 512 contiguous bytes per lane half,
+// already in MFMA operand format.
 // (HIP's second __launch_bounds__ argument is the minimum number of WAVES PER SIMD -- not CUDA's blocks per multiprocessor: 2 = the
 // 8 waves of the ONE workgroup a CU holds, i.e. a 256-register budget per wave; the 147 KB of LDS allow no second workgroup anyway)
-template <bool PLAIN>
+enum { WHOLE = 0, PLAIN = 1, TRUNK = 2 };                   // (the launch sets a.sigma_only = MODE + 1 for the two short tiles)
+template <int MODE>
 __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args8s A) {
     __shared__ uint4 lds[kPeU4 + kSlots * kSlotU4 + kBiasU4];
     const MlpArgs a = resolve_args(A.a);
@@ -240,11 +140,11 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
 #pragma unroll
             for (int b = 0; b < 8; ++b) quant16<true>(f[b], inv, X.h[b], X.l[b]);
             sx = scale_of(M);
-            if (st == 5 && !(PLAIN && a.sigma_only == 2)) {
+            if (st == 5 && !(MODE != WHOLE && a.sigma_only == MODE + 1)) {
                 fill_pe_wave(pw, true, a, row0, lane);                                  // the position encoding is done with: direction encoding
             }
         }
-        if (PLAIN && a.sigma_only == 2) {
+        if (MODE == PLAIN && a.sigma_only == 2) {
             // ---------------- the plain head: rows 0..3 of block 68 = output_linear's (r, g, b, sigma)
             i32x16 t;
             f32x16 fo;
@@ -255,6 +155,38 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
             if (g == 0 && i < a.n)
                 reinterpret_cast<float4*>(a.out)[sample_record(a, i)] = make_float4(fo[0] * up[0], fo[1] * up[1], fo[2] * up[2], fo[3] * up[3] * a.sigma_scale);
             R.off = (block_steps(0) + block_steps(1)) * nm::kStepBytes;                 // blocks 0 and 1 of the next tile are in flight: block 2 is next
+            continue;
+        }
+        if (MODE == TRUNK && a.sigma_only == 3) {
+            // ---------------- the trunk's end: the alpha row, and the live samples' activations to the colour head's list
+            i32x16 t;
+            f32x16 fa;
+            k_i8<8>(t, X, ring_enter(R, 68), R);
+            dequant16(fa, t, sx * (256.f * kappa[8]), bias + nm::stage_b_off(8) + 256);
+            const float sigma = fa[0] * u_sigma;
+            const float v = sigma * a.sigma_scale;                                      // (row 0 of the block: the g == 0 lane of a sample has it)
+            const int64_t i = row0 + s;
+            if (g == 0 && i < a.n) reinterpret_cast<float4*>(a.out)[sample_record(a, i)] = make_float4(0.f, 0.f, 0.f, v);
+            const unsigned live = (unsigned)__builtin_amdgcn_ballot_w64(g == 0 && i < a.n && !(v <= 0.f));      // bit s: sample s (a NaN is live)
+            if (live) {
+                int base = 0;
+                if (lane == 0) base = atomicAdd(A.live.count, __builtin_popcount(live));
+                base = __builtin_amdgcn_readfirstlane(base);
+                if ((live >> s) & 1) {
+                    const int64_t e = base + __builtin_popcount(live & ((1u << s) - 1u));
+                    uint4* dst = A.live.x + g * A.live.cap + e;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        dst[(4 * k) * A.live.cap] = X.h[k];
+                        dst[(4 * k + 2) * A.live.cap] = X.l[k];
+                    }
+                    if (g == 0) { A.live.sx[e] = sx; A.live.idx[e] = (int)i; }
+                }
+            }
+            // (the list stores, up to 19 per lane, and the atomic queue up BEHIND the copies of the next tile's blocks 0 and 1; the counted wait of the next
+            // ring_enter(R, 0) is right only because fill_pe_wave's sample loads at the top of the next tile wait vmcnt(0) first -- as the atomic's
+            // return and the exit's scratch reloads already do here: every tile's exit drains the ring's copies in flight, once per tile)
+            R.off = (block_steps(0) + block_steps(1)) * nm::kStepBytes;
             continue;
         }
         // ---------------- stage 8: alpha (row 0 of its block; first in the stream) + feature (linear, 256)
@@ -322,7 +254,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
 namespace nm {
 
 int launch_mlp_i8s(const MlpLaunch& L, const void* image8, const float* pts, const float* dirs, const float* origin, const float* direction,
-                   const float* z, int64_t n, int S, int in_mode, float sigma_scale, float* out, hipStream_t stream, const MlpChunk* chunk) {
+                   const float* z, int64_t n, int S, int in_mode, float sigma_scale, float* out, hipStream_t stream, const MlpChunk* chunk, const LiveList* live) {
     Args8s A;
     MlpArgs& a = A.a;
     a.ray_idx = chunk ? chunk->ray_idx : nullptr;
@@ -333,12 +265,13 @@ int launch_mlp_i8s(const MlpLaunch& L, const void* image8, const float* pts, con
     a.petab = L.petab;
     a.pts = pts; a.dirs = dirs; a.origin = origin; a.direction = direction; a.z = z;
     a.out = out; a.dbg = nullptr; a.prof = nullptr; a.n = n; a.S = S; a.in_mode = in_mode; a.stop_stage = -2; a.sigma_scale = sigma_scale;
-    a.sigma_only = L.plain_head ? 2 : 0;                                                // (PLAIN's exit after block 68)
+    a.sigma_only = L.plain_head ? 2 : live ? 3 : 0;                                     // (PLAIN's and TRUNK's exit after block 68)
     a.save_h = nullptr; a.save_hv = nullptr; a.save_bits = nullptr; a.save_h16 = nullptr; a.save_feat16 = nullptr; a.save_hvbits = nullptr; a.save_x0h = nullptr; a.save_d0h = nullptr;
     a.pos = PeSpec{L.pe_kind, L.pos_nfreq, L.pos_octaves};
     a.dir = PeSpec{L.pe_kind, L.dir_nfreq, L.dir_octaves};
     A.consts8 = L.consts8;
     A.image8 = reinterpret_cast<const uint4*>(image8);
+    A.live = live ? *live : LiveList{nullptr, nullptr, nullptr, nullptr, 0};
     const int64_t ntiles = (n + kTile - 1) / kTile;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess) {
@@ -346,8 +279,9 @@ int launch_mlp_i8s(const MlpLaunch& L, const void* image8, const float* pts, con
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
     }
     const int grid = (int)(ntiles < cus ? ntiles : cus);
-    if (L.plain_head) hipLaunchKernelGGL(nerf_mlp_i8s_kernel<true>, dim3(grid), dim3(kWaves * 64), 0, stream, A);
-    else hipLaunchKernelGGL(nerf_mlp_i8s_kernel<false>, dim3(grid), dim3(kWaves * 64), 0, stream, A);
+    if (L.plain_head) hipLaunchKernelGGL(nerf_mlp_i8s_kernel<PLAIN>, dim3(grid), dim3(kWaves * 64), 0, stream, A);
+    else if (live) hipLaunchKernelGGL(nerf_mlp_i8s_kernel<TRUNK>, dim3(grid), dim3(kWaves * 64), 0, stream, A);
+    else hipLaunchKernelGGL(nerf_mlp_i8s_kernel<WHOLE>, dim3(grid), dim3(kWaves * 64), 0, stream, A);
     return check_launch("nerf_mlp_i8s_kernel");
 }
 

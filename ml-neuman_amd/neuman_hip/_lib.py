@@ -56,6 +56,9 @@ SIGNATURES = {
     "nm_mlp_pack_bytes": (i64, [ctypes.POINTER(MlpDesc)]),
     "nm_mlp_pack_i8s_bytes": (i64, [ctypes.POINTER(MlpDesc)]),
     "nm_mlp_pack_i8s": (i32, [ctypes.POINTER(MlpDesc), ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
+    "nm_mlp_pack_i8s_trunk_bytes": (i64, [ctypes.POINTER(MlpDesc)]),
+    "nm_mlp_pack_i8s_head_bytes": (i64, [ctypes.POINTER(MlpDesc)]),
+    "nm_mlp_pack_i8s_live": (i32, [ctypes.POINTER(MlpDesc), ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p]),
     "nm_mlp_pack": (i32, [ctypes.POINTER(MlpDesc), ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
     "nm_mlp_pack_f16": (i32, [ctypes.POINTER(MlpDesc), ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p]),
     "nm_mlp_pack_i8_bytes": (i64, [ctypes.POINTER(MlpDesc)]),
@@ -77,6 +80,8 @@ SIGNATURES = {
     "nm_mlp_backward_chain16": (i32, [ctypes.c_void_p, ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_void_p, i64, c_f32p, ctypes.c_void_p, ctypes.c_void_p, c_f32p, c_f32p,
                                       c_f32p, c_f32p, i64, c_stream]),
     "nm_mlp_forward_rays": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, i32, ctypes.c_float, c_f32p, c_stream]),
+    "nm_mlp_forward_rays_live_workspace_bytes": (i64, [i64, i32, i64]),
+    "nm_mlp_forward_rays_live": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, i32, ctypes.c_float, c_f32p, ctypes.c_void_p, i64, i64, c_stream]),
     "nm_mlp_sigma_rays": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, i32, ctypes.c_float, c_f32p, c_stream]),
     "nm_mlp_forward_ray_chunk": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i32, c_i32p, c_i32p, i64, i32, i32, i32, ctypes.c_float, c_f32p,
                                        c_stream]),

@@ -354,9 +354,11 @@ def bkg_place_z(coarse_net, fine_net, o, d, near, far, samples_per_ray, importan
     return z_fine, None
 
 
-def bkg_shade(net, o, d, z, precision=None, trace=None, occluder=None, dz=None):
+def bkg_shade(net, o, d, z, precision=None, trace=None, occluder=None, dz=None, composite_only=False):
     """The background pass that is composited, on its final samples (render_utils.py:148-151, 294-297): whole, or -- TERMINATION_EPS > 0 --
-    marched front to back at eps (`occluder`, `dz`: march_pass_rays), or -- a grid attached (occupancy.attach) -- on its occupied samples"""
+    marched front to back at eps (`occluder`, `dz`: march_pass_rays), or -- a grid attached (occupancy.attach) -- on its occupied samples.
+    composite_only: the caller feeds the raw to raw2outputs and to nothing else, so the whole pass may leave the colour of a sample without
+    density at 0 (Joiner.forward_rays role='composite': its weight is exactly 0)"""
     if _occupancy_on(net):
         return _occupancy_pass(net, o, d, z, precision, 'shading', False, trace, 'occupancy')
     if TERMINATION_EPS > 0:
@@ -364,13 +366,13 @@ def bkg_shade(net, o, d, z, precision=None, trace=None, occluder=None, dz=None):
         raw = march_pass_rays(net, o, d, z, TERMINATION_EPS, precision=precision, stats=stats, occluder=occluder, dz=dz)
         _note(trace, march=stats)
         return raw
-    return net.forward_rays(o, d, z, precision=precision, role='shading')
+    return net.forward_rays(o, d, z, precision=precision, role='composite' if composite_only else 'shading')
 
 
 def bkg_pass_rays(coarse_net, fine_net, o, d, near, far, samples_per_ray, importance_samples_per_ray, white_bkg,
-                  precision=None, trace=None, given_z=None, occluder=None, dz=None):
+                  precision=None, trace=None, given_z=None, occluder=None, dz=None, composite_only=False):
     """Coarse (+ fine) background evaluation of R rays -> (raw [R,S',4], z [R,S'])  (render_utils.py:131-151, 287-297):
-    bkg_place_z + bkg_shade.
+    bkg_place_z + bkg_shade (`composite_only`: see there).
 
     `given_z` [R, S'] (tests only, like `trace`): replay recorded final sample positions instead of deriving them -- the shading
     network is evaluated on exactly those.  The renderers pass it from their `given` dict ({'bkg_z': [R,S'], 'near_far':
@@ -385,7 +387,7 @@ def bkg_pass_rays(coarse_net, fine_net, o, d, near, far, samples_per_ray, import
         return net.forward_rays(o, d, z, precision=precision, role='shading'), z
     z, raw = bkg_place_z(coarse_net, fine_net, o, d, near, far, samples_per_ray, importance_samples_per_ray, white_bkg, precision, trace)
     if raw is None:
-        raw = bkg_shade(net, o, d, z, precision, trace, occluder, dz)
+        raw = bkg_shade(net, o, d, z, precision, trace, occluder, dz, composite_only)
     _note(trace, bkg_z=z)
     return raw, z
 
@@ -401,7 +403,7 @@ def render_vanilla_rays(coarse_net, fine_net, o, d, near, far, samples_per_ray, 
         n = torch.full((j - i,), float(near), device=o.device, dtype=torch.float32)
         f = torch.full((j - i,), float(far), device=o.device, dtype=torch.float32)
         raw, z = bkg_pass_rays(coarse_net, fine_net, oc, dc, n, f, samples_per_ray, importance_samples_per_ray, white_bkg,
-                               precision, trace, given['bkg_z'][i:j] if given is not None and 'bkg_z' in given else None)
+                               precision, trace, given['bkg_z'][i:j] if given is not None and 'bkg_z' in given else None, composite_only=True)
         rgb[i:j], _, _, _, depth[i:j] = raw2outputs(raw, z, dc, white_bkg=white_bkg, want_weights=False)
     return rgb, depth
 

@@ -210,10 +210,11 @@ class Joiner(nn.Module):
         runs in i8x3; every other call (the coarse pass whose compositing weights place the importance samples, and any
         direct call) runs in fp16x3, whose sigma is float32 class (the inverse CDF amplifies a coarse-pass error by 1 / pdf:
         DESIGN.md section 5).  Sample positions are then bit-identical to the all-fp16x3 path and the colours differ from it
-        by the i8x3 compositing error (<= 2e-5, tests/test_hip_mlp.py) on every pixel."""
+        by the i8x3 compositing error (<= 2e-5, tests/test_hip_mlp.py) on every pixel.  role='composite' is 'shading' from a caller
+        whose raw feeds raw2outputs and nothing else (forward_rays)."""
         p = precision or self.precision
         if p == 'mixed':
-            p = 'i8x3' if role == 'shading' else 'fp16x3'
+            p = 'i8x3' if role in ('shading', 'composite') else 'fp16x3'
         return _lib.PRECISIONS[p]
 
     @staticmethod
@@ -265,13 +266,24 @@ class Joiner(nn.Module):
             return None
         return train.two_views(self, input_pts, input_views, other_views)
 
-    def forward_rays(self, origin, direction, z_vals, precision=None, sigma_scale=1.0, role=None, sigma_only=False):
+    def forward_rays(self, origin, direction, z_vals, precision=None, sigma_scale=1.0, role=None, sigma_only=False, chunk_samples=0):
         """Fused ray_to_samples point construction + forward: origin/direction [R,3], z_vals [R,S] -> [R,S,4].
         sigma_only: the caller uses nothing but out[..., 3] (a coarse pass that only places importance samples) -- the
-        colour head is skipped where the kernel can (out[..., :3] = 0), sigma is bit-identical either way."""
+        colour head is skipped where the kernel can (out[..., :3] = 0), sigma is bit-identical either way.
+        role='composite': the caller composites the result and does nothing else with it -- samples whose density is <= 0 (weight
+        exactly 0) come back with colour 0 and the colour head runs on the others only (nm_mlp_forward_rays_live, in chunks of
+        `chunk_samples`; 0: the library's default); every other record is bit-identical to role='shading'."""
         self._guard(origin, direction, z_vals)
         R, S = z_vals.shape
         out = torch.empty((R, S, 4), device=z_vals.device, dtype=torch.float32)
+        if role == 'composite' and not sigma_only and self.nerf.use_viewdirs and self._prec(precision, role) == _lib.NM_PREC_I8X3:
+            nbytes = _lib.lib().nm_mlp_forward_rays_live_workspace_bytes(R, S, int(chunk_samples))
+            ws = torch.empty((nbytes,), device=z_vals.device, dtype=torch.uint8)
+            _lib.check(_lib.lib().nm_mlp_forward_rays_live(
+                self.handle(), _lib.dev_ptr(origin, name='origin'), _lib.dev_ptr(direction, name='direction'), _lib.dev_ptr(z_vals, name='z_vals'), R, S,
+                self._prec(precision, role), float(sigma_scale), _lib.dev_ptr(out), _lib.dev_ptr(ws, torch.uint8), nbytes, int(chunk_samples),
+                _lib.stream_ptr()), "nm_mlp_forward_rays_live")
+            return out
         entry = _lib.lib().nm_mlp_sigma_rays if sigma_only else _lib.lib().nm_mlp_forward_rays
         _lib.check(entry(self.handle(), _lib.dev_ptr(origin, name='origin'), _lib.dev_ptr(direction, name='direction'),
                          _lib.dev_ptr(z_vals, name='z_vals'), R, S, self._prec(precision, role), float(sigma_scale),

@@ -1,0 +1,38 @@
+"""The bench frame's fine pass (640 000 rays x 256 samples on the bench's own sample positions): the whole-network launch (role='shading') against the
+trunk / head pair (role='composite', nm_mlp_forward_rays_live) at several chunk sizes -- HIP events, best and all of 3 -- and the live fraction the
+device finds.  profiles/live_heads.md records a run."""
+import os
+import sys
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, os.path.join(ROOT, "ml-neuman_amd"))
+import torch  # noqa: E402
+
+from neuman_hip import ray_utils, render_utils, synthetic  # noqa: E402
+
+dev = torch.device('cuda')
+coarse, fine = synthetic.make_joiner(0).to(dev), synthetic.make_joiner(1).to(dev)
+coarse.precision = fine.precision = 'mixed'
+cap = synthetic.SimpleCapture(800, 800)
+o, d = ray_utils.shot_all_rays_dev(cap, dev)
+R = o.shape[0]
+with torch.no_grad():
+    n = torch.full((R,), float(cap.near['bkg']), device=dev)
+    f = torch.full((R,), float(cap.far['bkg']), device=dev)
+    z, _ = render_utils.bkg_place_z(coarse, fine, o, d, n, f, 128, 128, True)
+    ref = fine.forward_rays(o, d, z, role='shading')
+    torch.cuda.synchronize()
+    live = int((ref[..., 3] > 0).sum())
+    print(f"rays {R}, samples {z.numel()}, live {live} = {live / z.numel():.4f}", flush=True)
+    for tag, kw in [('whole', dict(role='shading'))] + [(f'live 2^{k}', dict(role='composite', chunk_samples=1 << k)) for k in (20, 21, 22, 23, 24)] + [('whole', dict(role='shading')), ('live 2^22', dict(role='composite', chunk_samples=1 << 22))]:
+        ms = []
+        for _ in range(3):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fine.forward_rays(o, d, z, **kw)
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        same = torch.equal(out[..., 3], ref[..., 3]) and torch.equal(out[..., :3][ref[..., 3] > 0], ref[..., :3][ref[..., 3] > 0])
+        print(f"{tag:12s} best {min(ms):7.2f} ms  all {' '.join(f'{m:.2f}' for m in ms)}  live records equal: {same}", flush=True)
+        del out
