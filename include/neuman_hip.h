@@ -586,6 +586,8 @@ int nm_ssim_u8(const uint8_t* a, const uint8_t* b, int H, int W, int C, double* 
  *     zeros; table = the n_freqs bands (posenc) or the [3 n_freqs, 3] projection (rotate), device f32.
  *   nm_composite_backward: d loss / d raw [R,S,4] through raw2outputs given the gradients of rgb_map [R,3],
  *     acc_map [R], depth_map [R], weights [R,S] (each nullable = zero); disp_map's gradient is not supported.
+ *     d_raw must be 8-byte aligned (refused otherwise: the records double as f64 scratch); with raw and d_raw 16-byte
+ *     aligned and S <= 1024 a wave takes a ray, otherwise a lane does.
  * ------------------------------------------------------------------------------------------- */
 #define NM_GEMM_ACCUMULATE 1
 #define NM_GEMM_BIAS 2

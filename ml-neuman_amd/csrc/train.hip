@@ -1270,6 +1270,8 @@ int nm_composite_backward(const float* raw, const float* z_vals, const float* ra
     NM_REQUIRE(R >= 0 && S >= 1, "nm_composite_backward: bad sizes R=%lld S=%d", (long long)R, S);
     if (R == 0) return NM_OK;
     NM_REQUIRE(raw && z_vals && rays_d && d_raw, "nm_composite_backward: null pointer");
+    // the serial kernel keeps T_i as a double inside each d_raw record, and it is the kernel the misaligned callers get
+    NM_REQUIRE(((uintptr_t)d_raw & 7) == 0, "nm_composite_backward: d_raw must be 8-byte aligned (16 for the one-wave-per-ray kernel)");
     if (S <= 64 * kCbMax && (((uintptr_t)raw | (uintptr_t)d_raw) & 15) == 0) {
         hipLaunchKernelGGL(composite_backward_wave_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, nm::as_stream(stream), raw, z_vals, rays_d, R, S,
                            white_bkg, g_rgb, g_acc, g_depth, g_weights, d_raw);

@@ -51,7 +51,8 @@ def joiner_forward(W, pts, dirs, pos_freqs=10, dir_freqs=4, depth=8, skips=(4,),
 
 def raw2outputs(raw, z_vals, rays_d, white_bkg=True):
     dists = z_vals[..., 1:] - z_vals[..., :-1]
-    dists = torch.cat([dists, torch.full_like(dists[..., :1], 1e10)], -1) * torch.norm(rays_d[..., None, :], dim=-1)
+    # (the last interval taken from z_vals' shape, not dists': a one-sample ray has no difference to copy the shape of, and still ends in 1e10)
+    dists = torch.cat([dists, torch.full_like(z_vals[..., :1], 1e10)], -1) * torch.norm(rays_d[..., None, :], dim=-1)
     rgb = torch.sigmoid(raw[..., :3])
     alpha = 1. - torch.exp(-torch.relu(raw[..., 3]) * dists)
     T = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), 1. - alpha + 1e-10], -1), -1)[:, :-1]
