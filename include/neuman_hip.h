@@ -324,6 +324,38 @@ int nm_occ_compact_points(const uint32_t* bits, int res, const float* aabb, cons
                           int32_t* workspace, nm_stream_t stream);
 int nm_mlp_forward_listed(nm_mlp_t mlp, const float* pts, const float* dirs, int64_t n_points, const int32_t* point_idx, const int32_t* n_dev,
                           int64_t n_max, int precision, float sigma_scale, float* out, nm_stream_t stream);
+/* The colour head on live samples only (nm_mlp_forward_rays_live above) for the other input forms -- for a caller whose records are composited and
+ * nothing else: raw2outputs (utils/render_utils.py:85-95), alone or behind a sorted merge (:330-345, 441-456), reads a colour only as
+ * weight * sigmoid(colour), and the weight of an interval, a merged one included, is exactly 0 when the stored density is <= 0.
+ *   nm_mlp_forward_live            = nm_mlp_forward            (points and their own directions;         models/vanilla.py:162-166)
+ *   nm_mlp_forward_listed_live     = nm_mlp_forward_listed     (the listed points, each with dirs[k];    utils/render_utils.py:213-229)
+ *   nm_mlp_forward_samples_live    = nm_mlp_forward_samples    (the listed samples of rays;              utils/render_utils.py:139-151)
+ *   nm_mlp_forward_ray_chunk_live  = nm_mlp_forward_ray_chunk  (samples s0 .. s0+S-1 of the listed rays; utils/render_utils.py:139-151)
+ * Each takes its sibling's arguments, then workspace, workspace_bytes, chunk_samples before stream, and writes what the sibling writes except that
+ * the colour of a listed record whose stored density sigma * sigma_scale is <= 0 is (0, 0, 0): every density and every other listed record is
+ * BIT-IDENTICAL to the sibling's, every written value is finite, records that are not listed are not touched.  NM_PREC_I8X3 with the
+ * view-dependent head; any other precision, the plain-head net and NEUMAN_I8_KERNEL=w run the sibling itself.  The input is walked in pieces of
+ * at most chunk_samples entries (<= 0: NM_LIVE_CHUNK_SAMPLES; for nm_mlp_forward_ray_chunk_live a piece is a whole number of listed rays, so
+ * chunk_samples must be at least S): per piece a counter reset, a trunk launch and a head launch.  Where the list's length lives on the device
+ * (n_dev, n_rays_dev), piece p covers clamp(*n_dev - p * piece, 0, piece) entries: one small kernel computes these into the workspace before the
+ * first trunk launch, and an empty piece launches over a count of 0.  No host synchronisation, no allocation.  out and workspace must be
+ * 16-byte aligned; with NM_PREC_I8X3 the workspace holds nm_mlp_live_workspace_bytes(n_max, chunk_samples) bytes (n_max = n, n_max, or
+ * n_rays * S) whichever net is behind the handle: one piece with every entry live, 520 B per entry with the piece = min(n_max, chunk_samples)
+ * rounded up to 256, plus the counters.  These argument errors are reported before the handle is looked at and before anything is enqueued.
+ * out of nm_mlp_forward_ray_chunk_live holds fewer than 2^31 records (the list carries a record as int32). */
+int64_t nm_mlp_live_workspace_bytes(int64_t n_max, int64_t chunk_samples);
+int nm_mlp_forward_live(nm_mlp_t mlp, const float* pts, const float* dirs, int64_t n, int precision, float sigma_scale, float* out, void* workspace,
+                        int64_t workspace_bytes, int64_t chunk_samples, nm_stream_t stream);
+int nm_mlp_forward_listed_live(nm_mlp_t mlp, const float* pts, const float* dirs, int64_t n_points, const int32_t* point_idx, const int32_t* n_dev,
+                               int64_t n_max, int precision, float sigma_scale, float* out, void* workspace, int64_t workspace_bytes,
+                               int64_t chunk_samples, nm_stream_t stream);
+int nm_mlp_forward_samples_live(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S,
+                                const int32_t* sample_idx, const int32_t* n_dev, int64_t n_max, int precision, float sigma_scale, float* out,
+                                void* workspace, int64_t workspace_bytes, int64_t chunk_samples, nm_stream_t stream);
+int nm_mlp_forward_ray_chunk_live(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int S_total,
+                                  const int32_t* ray_idx, const int32_t* n_rays_dev, int64_t n_rays, int s0, int S, int precision,
+                                  float sigma_scale, float* out, void* workspace, int64_t workspace_bytes, int64_t chunk_samples,
+                                  nm_stream_t stream);
 /* T[r] *= prod_{i in chunk} (1 - alpha_i + 1e-10) for the listed rays (ray_idx nullable = rays 0..n_rays-1): the
  * transmittance factors of raw2outputs (render_utils.py:85-95) over samples s0 .. s0+S-1 of raw [R,S_total,4]; rays whose T
  * falls below the caller's epsilon are dropped by nm_compact_hits(eps, T). */
@@ -485,6 +517,33 @@ int nm_render_rays_hybrid(nm_mlp_t coarse, nm_mlp_t fine, nm_mlp_t human, nm_mes
                           double geo_threshold, const float* origin, const float* direction, int64_t R, float bkg_near, float bkg_far, int S, int N,
                           int S_human, const float* t_vals, const float* u, const float* t_vals_human, int white_bkg, int precision_coarse,
                           int precision_fine, int precision_human, float* workspace, float* rgb, float* depth, float* acc, nm_stream_t stream);
+/* The four calls above with the pass that is COMPOSITED -- the single or the fine background pass (utils/render_utils.py:148-151, 294-297), the
+ * human pass (:213-229, 320-329) -- run as nm_mlp_forward_rays_live / nm_mlp_forward_live / nm_mlp_forward_samples_live /
+ * nm_mlp_forward_listed_live: for a caller whose raw_out reaches raw2outputs (:85-95), alone or behind a sorted merge (:330-345, 441-456), and
+ * nothing else.  raw_out differs from the sibling's only in the colours of samples whose stored density is <= 0, which are 0; rgb, depth and acc
+ * are BIT-IDENTICAL.  The coarse pass of a two-pass background still runs nm_mlp_sigma_rays.  Each takes its sibling's arguments, then
+ * live_ws (16-byte aligned), live_ws_bytes, chunk_samples (<= 0: NM_LIVE_CHUNK_SAMPLES; at least one ray's samples): the passes of one call use
+ * live_ws one after another, so it holds nm_mlp_live_workspace_bytes(n, chunk_samples) bytes for the largest composited pass of the call that
+ * runs in NM_PREC_I8X3 -- n = R (S + N), R S, or for nm_render_rays_hybrid_live the larger of R (S + N) and R S_human.  These are checked
+ * before anything is enqueued.  The plain entries enqueue exactly what they did before these existed (one body serves both). */
+int nm_render_rays_bkg_live(nm_mlp_t coarse, nm_mlp_t fine, const float* origin, const float* direction, const float* near, const float* far,
+                            int64_t R, int S, int N, const float* t_vals, const float* u, int white_bkg, int precision_coarse, int precision_fine,
+                            float* workspace, float* raw_out, float* z_out, float* rgb, float* depth, float* acc, void* live_ws,
+                            int64_t live_ws_bytes, int64_t chunk_samples, nm_stream_t stream);
+int nm_render_rays_human_live(nm_mlp_t human, nm_mesh_t mesh, const double* T, const float* origin, const float* direction, const float* near,
+                              const float* far, int64_t R, int S, const float* t_vals, int white_bkg, float sigma_scale, int precision,
+                              float* workspace, float* raw_out, float* z_out, float* rgb, float* depth, float* acc, void* live_ws,
+                              int64_t live_ws_bytes, int64_t chunk_samples, nm_stream_t stream);
+int nm_render_rays_human_occ_live(nm_mlp_t human, nm_mesh_t mesh, const double* T, const uint32_t* bits, int res, const float* aabb,
+                                  const float* origin, const float* direction, const float* near, const float* far, int64_t R, int S,
+                                  const float* t_vals, int white_bkg, float sigma_scale, int precision, float* workspace, float* raw_out,
+                                  float* z_out, int32_t* counts, float* rgb, float* depth, float* acc, void* live_ws, int64_t live_ws_bytes,
+                                  int64_t chunk_samples, nm_stream_t stream);
+int nm_render_rays_hybrid_live(nm_mlp_t coarse, nm_mlp_t fine, nm_mlp_t human, nm_mesh_t mesh, const double* T, const float* verts, int V,
+                               double geo_threshold, const float* origin, const float* direction, int64_t R, float bkg_near, float bkg_far, int S,
+                               int N, int S_human, const float* t_vals, const float* u, const float* t_vals_human, int white_bkg,
+                               int precision_coarse, int precision_fine, int precision_human, float* workspace, float* rgb, float* depth,
+                               float* acc, void* live_ws, int64_t live_ws_bytes, int64_t chunk_samples, nm_stream_t stream);
 /* ONE KERNEL for the merge + composite tail of the hybrid renderers (utils/render_utils.py:330-345, 441-456): k <= 4 sorted lists per
  * ray (z[l] [.,S[l]], raw[l] [.,S[l],4]; rows[l] nullable: list l's arrays are indexed by rows[l][ray] -- e.g. the background arrays of
  * ALL rays read in place for the hit rays) -> the merged order (ties: the earlier list first, exactly what nm_merge_sorted applied list

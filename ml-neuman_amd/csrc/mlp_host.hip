@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "common.h"
+#include <string>
 #include "mlp_layout.h"
 #include "mlp_launch.h"
 
@@ -1126,7 +1127,7 @@ int nm_mlp_forward_rays_live(nm_mlp_t m, const float* origin, const float* direc
         if (int rc = nm::launch_mlp_i8s(L, m->d_trunk8, nullptr, nullptr, origin + r0 * 3, direction + r0 * 3, z_vals + r0 * S, nr * S, S, 1, sigma_scale, o, st,
                                         nullptr, &live))
             return rc;
-        if (int rc = nm::launch_mlp_i8h(L, m->d_trunk8 + nm::kTrunkStreamBytes8, direction + r0 * 3, S, live, nr * S, o, st)) return rc;
+        if (int rc = nm::launch_mlp_i8h(L, m->d_trunk8 + nm::kTrunkStreamBytes8, 3, nullptr, direction + r0 * 3, S, live, nr * S, o, st)) return rc;
     }
     return NM_OK;
 }
@@ -1191,6 +1192,16 @@ int nm_mlp_sigma_samples(nm_mlp_t mlp, const float* origin, const float* directi
 
 bool nm::mlp_plain_head(nm_mlp_t m) { return m && m->desc.plain_head; }
 
+namespace {
+// entries of piece p of a list whose length *n_dev lives on the device: clamp(*n_dev - p * piece, 0, piece)
+__global__ void live_piece_lengths_kernel(const int* __restrict__ n_dev, int piece, int npieces, int* __restrict__ len) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npieces) return;
+    const int64_t left = (int64_t)*n_dev - (int64_t)p * piece;
+    len[p] = (int)(left < 0 ? 0 : left > piece ? piece : left);
+}
+}  // namespace
+
 extern "C" {
 
 int nm_mlp_forward_listed(nm_mlp_t mlp, const float* pts, const float* dirs, int64_t n_points, const int32_t* point_idx, const int32_t* n_dev,
@@ -1202,6 +1213,128 @@ int nm_mlp_forward_listed(nm_mlp_t mlp, const float* pts, const float* dirs, int
     NM_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "nm_mlp_forward_listed: out must be 16-byte aligned");
     nm::MlpChunk c{point_idx, n_dev, 0, 1};
     return mlp_dispatch(mlp, pts, dirs, nullptr, nullptr, nullptr, n_max, 1, 4, precision, -2, sigma_scale, out, nullptr, stream, nullptr, 0, &c);
+}
+
+// ---- the same pair for the other input forms (points, listed points, listed samples, a chunk of listed rays): the trunk lists every live sample's
+// RECORD in `out` (sample_record), so the head needs nothing but the direction that goes with a record
+static int64_t live_piece(int64_t n_max, int64_t chunk_samples) {                       // entries of one piece
+    if (chunk_samples <= 0) chunk_samples = NM_LIVE_CHUNK_SAMPLES;
+    return n_max < chunk_samples ? n_max : chunk_samples;
+}
+// an upper bound of the pieces of any form: a piece of whole rays (in_mode 2) holds more than half of chunk_samples
+static int64_t live_pieces_bound(int64_t n_max, int64_t chunk_samples) {
+    if (chunk_samples <= 0) chunk_samples = NM_LIVE_CHUNK_SAMPLES;
+    return 2 * ((n_max + chunk_samples - 1) / chunk_samples) + 2;
+}
+
+int64_t nm_mlp_live_workspace_bytes(int64_t n_max, int64_t chunk_samples) {
+    if (n_max < 0) return -1;
+    const int64_t cap = (live_piece(n_max, chunk_samples) + 255) / 256 * 256;
+    return cap * (512 + 4 + 4) + 256 + (live_pieces_bound(n_max, chunk_samples) * 4 + 255) / 256 * 256;
+}
+
+// what every entry checks before it looks at the handle (so that a bad call fails the same way with or without a device)
+#define NM_LIVE_REQUIRE(who, n_max)                                                                                                                        \
+    NM_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0, who ": out and workspace must be 16-byte aligned"); \
+    NM_REQUIRE((n_max) >= 0, who ": bad sizes");                                                                                                           \
+    NM_REQUIRE(precision != NM_PREC_I8X3 || ((workspace || (n_max) == 0) && workspace_bytes >= nm_mlp_live_workspace_bytes(n_max, chunk_samples)),         \
+               who ": workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)nm_mlp_live_workspace_bytes(n_max, chunk_samples));    \
+    NM_REQUIRE(mlp, who ": null handle")
+
+static bool live_route(nm_mlp_t m, int precision) { return !m->desc.plain_head && precision == NM_PREC_I8X3 && i8_as_kernel(); }
+
+// in_mode 0: pts / dirs [n_units, 3]; 4: idx lists points; 3: idx lists samples r * S + s of z [., S]; 2: idx lists rays, S samples from s0 of z [., S_total].
+// n_units: entries (rays for in_mode 2), an upper bound when n_dev is given
+static int forward_live(const char* who, nm_mlp_t m, int in_mode, const float* pts, const float* dirs, const float* origin, const float* direction, const float* z,
+                        int S, int S_total, int s0, const int32_t* idx, const int32_t* n_dev, int64_t n_units, float sigma_scale, float* out, void* workspace,
+                        int64_t chunk_samples, nm_stream_t stream) {
+    if (n_units == 0) return NM_OK;
+    const int64_t unit = in_mode == 2 ? S : 1, n_max = n_units * unit;
+    const int64_t cap = (live_piece(n_max, chunk_samples) + 255) / 256 * 256;
+    int64_t piece = live_piece(n_max, chunk_samples) / unit;                            // units of one piece: whole rays
+    NM_REQUIRE(piece >= 1, "%s: chunk_samples holds no whole ray of %d samples", who, S);
+    const int64_t npieces = (n_units + piece - 1) / piece;
+    NM_REQUIRE(piece * unit < (1ll << 31) && npieces <= live_pieces_bound(n_max, chunk_samples), "%s: a piece of %lld samples", who, (long long)(piece * unit));
+    nm::MlpLaunch L;
+    L.wpack = nullptr; L.bias = nullptr; L.wpack16 = nullptr; L.bias16 = nullptr; L.wstream8 = nullptr;
+    L.petab = m->d_petab;
+    L.pe_kind = m->desc.pe_kind; L.pos_nfreq = m->desc.pos_n_freqs; L.dir_nfreq = m->desc.dir_n_freqs;
+    L.pos_octaves = m->pos_octaves; L.dir_octaves = m->dir_octaves;
+    L.plain_head = 0;
+    L.consts8 = m->d_consts8;
+    uint8_t* ws = static_cast<uint8_t*>(workspace);
+    nm::LiveList live;
+    live.x = reinterpret_cast<uint4*>(ws);
+    live.sx = reinterpret_cast<float*>(ws + cap * 512);
+    live.idx = reinterpret_cast<int*>(ws + cap * 516);
+    live.count = reinterpret_cast<int*>(ws + cap * 520);
+    live.cap = cap;
+    int* piece_len = reinterpret_cast<int*>(ws + cap * 520 + 256);
+    hipStream_t st = nm::as_stream(stream);
+    if (n_dev) {
+        hipLaunchKernelGGL(live_piece_lengths_kernel, dim3((unsigned)((npieces + 255) / 256)), dim3(256), 0, st, n_dev, (int)piece, (int)npieces, piece_len);
+        if (int rc = nm::check_launch("live_piece_lengths_kernel")) return rc;
+    }
+    const uint8_t* head8 = m->d_trunk8 + nm::kTrunkStreamBytes8;
+    for (int64_t p = 0; p < npieces; ++p) {                                             // per piece: counter reset, trunk launch, head launch
+        const int64_t u0 = p * piece, nu = n_units - u0 < piece ? n_units - u0 : piece;
+        if (int rc = nm::check_hip(hipMemsetAsync(live.count, 0, 4, st), (std::string(who) + ": counter reset").c_str())) return rc;
+        if (in_mode == 0) {                                                             // the piece is a launch of its own: records are local to it
+            if (int rc = nm::launch_mlp_i8s(L, m->d_trunk8, pts + u0 * 3, dirs + u0 * 3, nullptr, nullptr, nullptr, nu, 1, 0, sigma_scale, out + u0 * 4, st, nullptr, &live))
+                return rc;
+            if (int rc = nm::launch_mlp_i8h(L, head8, 4, dirs + u0 * 3, nullptr, 1, live, nu, out + u0 * 4, st)) return rc;
+            continue;
+        }
+        const nm::MlpChunk c{idx + u0, n_dev ? piece_len + p : nullptr, s0, S_total};   // the piece is a stretch of the list: records are the caller's
+        if (int rc = nm::launch_mlp_i8s(L, m->d_trunk8, pts, dirs, origin, direction, z, nu * unit, S, in_mode, sigma_scale, out, st, &c, &live)) return rc;
+        if (int rc = nm::launch_mlp_i8h(L, head8, in_mode == 4 ? 4 : 3, dirs, direction, S_total, live, nu * unit, out, st)) return rc;
+    }
+    return NM_OK;
+}
+
+int nm_mlp_forward_live(nm_mlp_t mlp, const float* pts, const float* dirs, int64_t n, int precision, float sigma_scale, float* out, void* workspace,
+                        int64_t workspace_bytes, int64_t chunk_samples, nm_stream_t stream) {
+    NM_LIVE_REQUIRE("nm_mlp_forward_live", n);
+    if (!live_route(mlp, precision)) return nm_mlp_forward(mlp, pts, dirs, n, precision, sigma_scale, out, stream);
+    NM_REQUIRE(n == 0 || (pts && dirs && out), "nm_mlp_forward_live: null pointer");
+    return forward_live("nm_mlp_forward_live", mlp, 0, pts, dirs, nullptr, nullptr, nullptr, 1, 1, 0, nullptr, nullptr, n, sigma_scale, out, workspace, chunk_samples, stream);
+}
+
+int nm_mlp_forward_listed_live(nm_mlp_t mlp, const float* pts, const float* dirs, int64_t n_points, const int32_t* point_idx, const int32_t* n_dev, int64_t n_max,
+                               int precision, float sigma_scale, float* out, void* workspace, int64_t workspace_bytes, int64_t chunk_samples, nm_stream_t stream) {
+    NM_LIVE_REQUIRE("nm_mlp_forward_listed_live", n_max);
+    if (!live_route(mlp, precision)) return nm_mlp_forward_listed(mlp, pts, dirs, n_points, point_idx, n_dev, n_max, precision, sigma_scale, out, stream);
+    NM_REQUIRE(n_max == 0 || (pts && dirs && point_idx && out), "nm_mlp_forward_listed_live: null pointer");
+    NM_REQUIRE(n_points >= 0 && n_max <= n_points && n_points < (1ll << 31), "nm_mlp_forward_listed_live: bad sizes (n_points=%lld n_max=%lld)", (long long)n_points,
+               (long long)n_max);
+    return forward_live("nm_mlp_forward_listed_live", mlp, 4, pts, dirs, nullptr, nullptr, nullptr, 1, 1, 0, point_idx, n_dev, n_max, sigma_scale, out, workspace,
+                        chunk_samples, stream);
+}
+
+int nm_mlp_forward_samples_live(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S, const int32_t* sample_idx,
+                                const int32_t* n_dev, int64_t n_max, int precision, float sigma_scale, float* out, void* workspace, int64_t workspace_bytes,
+                                int64_t chunk_samples, nm_stream_t stream) {
+    NM_LIVE_REQUIRE("nm_mlp_forward_samples_live", n_max);
+    if (!live_route(mlp, precision))
+        return nm_mlp_forward_samples(mlp, origin, direction, z_vals, R, S, sample_idx, n_dev, n_max, precision, sigma_scale, out, stream);
+    NM_REQUIRE(n_max == 0 || (origin && direction && z_vals && sample_idx && out), "nm_mlp_forward_samples_live: null pointer");
+    NM_REQUIRE(R >= 0 && S >= 1 && n_max <= R * (int64_t)S && R * (int64_t)S < (1ll << 31), "nm_mlp_forward_samples_live: bad sizes (R=%lld S=%d n_max=%lld)", (long long)R, S,
+               (long long)n_max);
+    return forward_live("nm_mlp_forward_samples_live", mlp, 3, nullptr, nullptr, origin, direction, z_vals, S, S, 0, sample_idx, n_dev, n_max, sigma_scale, out, workspace,
+                        chunk_samples, stream);
+}
+
+int nm_mlp_forward_ray_chunk_live(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int S_total, const int32_t* ray_idx,
+                                  const int32_t* n_rays_dev, int64_t n_rays, int s0, int S, int precision, float sigma_scale, float* out, void* workspace,
+                                  int64_t workspace_bytes, int64_t chunk_samples, nm_stream_t stream) {
+    NM_REQUIRE(S >= 1, "nm_mlp_forward_ray_chunk_live: bad sizes (S=%d)", S);
+    NM_LIVE_REQUIRE("nm_mlp_forward_ray_chunk_live", n_rays * (int64_t)S);
+    if (!live_route(mlp, precision))
+        return nm_mlp_forward_ray_chunk(mlp, origin, direction, z_vals, S_total, ray_idx, n_rays_dev, n_rays, s0, S, precision, sigma_scale, out, stream);
+    NM_REQUIRE(n_rays == 0 || (origin && direction && z_vals && ray_idx && out), "nm_mlp_forward_ray_chunk_live: null pointer");
+    NM_REQUIRE(s0 >= 0 && s0 + S <= S_total, "nm_mlp_forward_ray_chunk_live: bad sizes (s0=%d S=%d S_total=%d)", s0, S, S_total);
+    return forward_live("nm_mlp_forward_ray_chunk_live", mlp, 2, nullptr, nullptr, origin, direction, z_vals, S, S_total, s0, ray_idx, n_rays_dev, n_rays, sigma_scale, out,
+                        workspace, chunk_samples, stream);
 }
 
 int nm_mlp_forward_profile(nm_mlp_t mlp, const float* pts, const float* dirs, int64_t n, int precision, float* out,

@@ -1,9 +1,10 @@
-// NM_PREC_I8X3, the colour head alone: the second launch of nm_mlp_forward_rays_live.  The trunk launch (mlp_i8s.hip TRUNK) has written every
+// NM_PREC_I8X3, the colour head alone: the second launch of nm_mlp_forward_rays_live and the other nm_mlp_forward_*_live entries.  The trunk launch (mlp_i8s.hip TRUNK) has written every
 // sample's density and listed the samples compositing can see (stored density not <= 0) with their quantised stage-7 activations; this kernel runs
 // feature_linear, the views layer and rgb_linear -- ring blocks 69..81 of nerf_mlp_i8s_kernel's tile, 324 of its 1884 MFMAs per 32 samples -- on the
 // listed samples only and writes their colours beside the densities.  Same workgroup shape, ring and helpers (mlp_i8as.h), and operation for operation
 // the arithmetic of that kernel's stages 8 (features), 9 and 10: a listed sample's record is bit-identical to the whole-network launch's.
-// A wave's 32 samples are 32 consecutive list entries: whatever rays they come from, each takes its direction encoding from its own ray.
+// A wave's 32 samples are 32 consecutive list entries: whatever rays they come from, each takes its direction encoding from its own ray (in_mode 3:
+// the entry is the record r * S_total + s of a ray form) or from its own point's direction (in_mode 4: the entry is the record k of a point form).
 //
 // Reference semantics: models/vanilla.py NeRF.forward (:136-144).
 #include "mlp_i8as.h"
@@ -24,7 +25,7 @@ typedef RingT<HeadStream> Ring;
 
 __global__ __launch_bounds__(kWaves * 64, 2) void nerf_head_i8s_kernel(const Args8s A) {
     __shared__ uint4 lds[kPeU4 + kSlots * kSlotU4 + kBiasU4];
-    const MlpArgs a = resolve_args(A.a);                                               // in_mode 3 over the list: a.n = its length
+    const MlpArgs a = resolve_args(A.a);                                               // in_mode 3 / 4 over the list: a.n = its length
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int g = lane >> 5, s = lane & 31;
@@ -128,18 +129,18 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_head_i8s_kernel(const Arg
 
 namespace nm {
 
-int launch_mlp_i8h(const MlpLaunch& L, const void* head8, const float* direction, int S, const LiveList& live, int64_t max_entries, float* out,
-                   hipStream_t stream) {
+int launch_mlp_i8h(const MlpLaunch& L, const void* head8, int in_mode, const float* dirs, const float* direction, int S_total, const LiveList& live,
+                   int64_t max_entries, float* out, hipStream_t stream) {
     Args8s A;
     MlpArgs& a = A.a;
-    a.ray_idx = live.idx;
-    a.n_rays_dev = live.count;
+    a.ray_idx = live.idx;                                                               // the records the trunk listed: out[rec], and the direction of
+    a.n_rays_dev = live.count;                                                          // ray rec / S_total (in_mode 3) or dirs[rec] itself (in_mode 4)
     a.s0 = 0;
-    a.S_total = S;
+    a.S_total = S_total;
     a.wpack = nullptr; a.bias = nullptr;
     a.petab = L.petab;
-    a.pts = nullptr; a.dirs = nullptr; a.origin = nullptr; a.direction = direction; a.z = nullptr;
-    a.out = out; a.dbg = nullptr; a.prof = nullptr; a.n = max_entries; a.S = S; a.in_mode = 3; a.stop_stage = -2; a.sigma_scale = 1.f;
+    a.pts = nullptr; a.dirs = dirs; a.origin = nullptr; a.direction = direction; a.z = nullptr;
+    a.out = out; a.dbg = nullptr; a.prof = nullptr; a.n = max_entries; a.S = S_total; a.in_mode = in_mode; a.stop_stage = -2; a.sigma_scale = 1.f;
     a.sigma_only = 0;
     a.save_h = nullptr; a.save_hv = nullptr; a.save_bits = nullptr; a.save_h16 = nullptr; a.save_feat16 = nullptr; a.save_hvbits = nullptr; a.save_x0h = nullptr; a.save_d0h = nullptr;
     a.pos = PeSpec{L.pe_kind, L.pos_nfreq, L.pos_octaves};

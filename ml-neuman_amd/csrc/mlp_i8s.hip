@@ -41,10 +41,10 @@ typedef RingT<TileStream> Ring;
 // stays the default one's, and the STREAM is cut to fit it (mlp_host.hip pack_stream8s): where the look-ahead expects blocks 69 and 70 (8 steps each)
 // it finds the next tile's blocks 0 and 1 (4 steps each, padded to 8), and the exit points the ring at block 2.  The exit tests a.sigma_only == 2 (set by
 // the launch) rather than PLAIN alone, so that the code after it stays in the instantiation: without it the allocation of the stage loop changes too.
-// TRUNK: the first of the two launches that shade live samples only (mlp_i8h.hip is the second; nm_mlp_forward_rays_live): the same exit after block 68 on
+// TRUNK: the first of the two launches that shade live samples only (mlp_i8h.hip is the second; nm_mlp_forward_rays_live, nm_mlp_forward_*_live): the same exit after block 68 on
 // the whole net's stream cut the same way.  It writes (0, 0, 0, sigma) and, for every sample whose stored density is not <= 0 -- the only ones whose colour
 // compositing can see: alpha = 1 - exp(-relu(sigma) dist) is exactly 0 otherwise -- appends what the colour head needs to a global list: the stage-7
-// activations it holds (X: 512 B), their row scale and the sample's index.  One ballot, one prefix count and one atomic add per wave; the list is
+// activations it holds (X: 512 B), their row scale and the sample's record in `out` (whatever the input mode).  One ballot, one prefix count and one atomic add per wave; the list is
 // [piece 2 t + limb][lane half g][entry][16 B], so that the head's wave loads 32 consecutive entries of a piece as 512 contiguous bytes per lane half,
 // already in MFMA operand format.
 // (HIP's second __launch_bounds__ argument is the minimum number of WAVES PER SIMD -- not CUDA's blocks per multiprocessor: 2 = the
@@ -166,7 +166,8 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
             const float sigma = fa[0] * u_sigma;
             const float v = sigma * a.sigma_scale;                                      // (row 0 of the block: the g == 0 lane of a sample has it)
             const int64_t i = row0 + s;
-            if (g == 0 && i < a.n) reinterpret_cast<float4*>(a.out)[sample_record(a, i)] = make_float4(0.f, 0.f, 0.f, v);
+            const int64_t rec = g == 0 && i < a.n ? sample_record(a, i) : 0;          // the sample's record in `out`: what the head's list carries
+            if (g == 0 && i < a.n) reinterpret_cast<float4*>(a.out)[rec] = make_float4(0.f, 0.f, 0.f, v);
             const unsigned live = (unsigned)__builtin_amdgcn_ballot_w64(g == 0 && i < a.n && !(v <= 0.f));      // bit s: sample s (a NaN is live)
             if (live) {
                 int base = 0;
@@ -180,7 +181,7 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
                         dst[(4 * k) * A.live.cap] = X.h[k];
                         dst[(4 * k + 2) * A.live.cap] = X.l[k];
                     }
-                    if (g == 0) { A.live.sx[e] = sx; A.live.idx[e] = (int)i; }
+                    if (g == 0) { A.live.sx[e] = sx; A.live.idx[e] = (int)rec; }
                 }
             }
             // (the list stores, up to 19 per lane, and the atomic queue up BEHIND the copies of the next tile's blocks 0 and 1; the counted wait of the next

@@ -44,7 +44,7 @@ int launch_mlp_mfma(const MlpLaunch& L, const float* pts, const float* dirs, con
                     float* dbg, void* prof, hipStream_t stream, int sigma_only = 0, const MlpChunk* chunk = nullptr);
 // the list between the two launches that evaluate the colour head on live samples only (stored density not <= 0): the trunk launch appends, the head
 // launch reads.  x: [16 pieces = 2 k-step + limb][2 lane halves][cap][16 B], the quantised stage-7 activations as the MFMA's B fragments; sx [cap] their
-// row scales; idx [cap] the flat sample index r * S + s within the launch; *count the list's length (reset to 0 before the trunk launch)
+// row scales; idx [cap] the sample's record in the launch's `out` (sample_record); *count the list's length (reset to 0 before the trunk launch)
 struct LiveList {
     uint4* x; float* sx; int* idx; int* count; int64_t cap;
 };
@@ -53,10 +53,11 @@ struct LiveList {
 int launch_mlp_i8s(const MlpLaunch& L, const void* image8, const float* pts, const float* dirs, const float* origin, const float* direction,
                    const float* z, int64_t n, int S, int in_mode, float sigma_scale, float* out, hipStream_t stream, const MlpChunk* chunk,
                    const LiveList* live = nullptr);
-// ... and the head launch (mlp_i8h.hip): stages 8 (features), 9 and 10 on the listed samples of rays [*, S]; head8 = ring blocks 69..81 of the stream;
-// max_entries bounds the grid (the length itself is read on the device)
-int launch_mlp_i8h(const MlpLaunch& L, const void* head8, const float* direction, int S, const LiveList& live, int64_t max_entries, float* out,
-                   hipStream_t stream);
+// ... and the head launch (mlp_i8h.hip): stages 8 (features), 9 and 10 on the listed records of `out`; head8 = ring blocks 69..81 of the stream.
+// in_mode 3 (the trunk ran a ray form, in_mode 1, 2 or 3): record r * S_total + s takes direction[r]; in_mode 4 (the trunk ran a point form, in_mode 0
+// or 4): record k takes dirs[k].  max_entries bounds the grid (the length itself is read on the device)
+int launch_mlp_i8h(const MlpLaunch& L, const void* head8, int in_mode, const float* dirs, const float* direction, int S_total, const LiveList& live,
+                   int64_t max_entries, float* out, hipStream_t stream);
 // NM_PREC_FP16X3 density only, activation-stationary (mlp_f16t.hip); stream16t = sigma_stream_kernel's re-cut of the fp16 image.  dbg (nullable): the
 // activations after stage dbg_stage of the first tile (+ 100 x round) of workgroup 0 as float32 [128 samples][256] in k-slot order
 int sigma_f16t_ndir();       // the NDIR tools/gen_f16t.py emitted mlp_f16t_body.h for: the stream is cut for exactly that

@@ -4,10 +4,41 @@
 // as the step-by-step entry points.  Reference: utils/render_utils.py:131-151 / 287-297 (two-pass background), :213-229 / 320-329
 // (human pass of already compacted hit rays), :330-345 / 441-456 (merge + composite).
 #include "common.h"
+#include <string>
 
 namespace {
 inline int64_t align4(int64_t n) { return (n + 3) & ~int64_t(3); }        // keep every sub-array 16-byte aligned
+
+// The pass of a call whose output is composited and nothing else, in its two forms: the whole-network launch (lw == nullptr: what the plain
+// entries enqueue), or the trunk / colour-head pair on live samples only (the *_live entries: nm_mlp_forward_*_live).  The passes of one call
+// use the workspace one after another.
+struct LiveWs {
+    void* ws; int64_t bytes; int64_t chunk;
+};
+int shade_rays(const LiveWs* lw, nm_mlp_t m, const float* o, const float* d, const float* z, int64_t R, int S, int prec, float scale, float* out, nm_stream_t st) {
+    return lw ? nm_mlp_forward_rays_live(m, o, d, z, R, S, prec, scale, out, lw->ws, lw->bytes, lw->chunk, st) : nm_mlp_forward_rays(m, o, d, z, R, S, prec, scale, out, st);
+}
+int shade_points(const LiveWs* lw, nm_mlp_t m, const float* pts, const float* dirs, int64_t n, int prec, float scale, float* out, nm_stream_t st) {
+    return lw ? nm_mlp_forward_live(m, pts, dirs, n, prec, scale, out, lw->ws, lw->bytes, lw->chunk, st) : nm_mlp_forward(m, pts, dirs, n, prec, scale, out, st);
+}
+int shade_samples(const LiveWs* lw, nm_mlp_t m, const float* o, const float* d, const float* z, int64_t R, int S, const int32_t* idx, const int32_t* n_dev, int prec,
+                  float scale, float* out, nm_stream_t st) {
+    return lw ? nm_mlp_forward_samples_live(m, o, d, z, R, S, idx, n_dev, R * S, prec, scale, out, lw->ws, lw->bytes, lw->chunk, st)
+              : nm_mlp_forward_samples(m, o, d, z, R, S, idx, n_dev, R * S, prec, scale, out, st);
+}
+int shade_listed(const LiveWs* lw, nm_mlp_t m, const float* pts, const float* dirs, int64_t n, const int32_t* idx, const int32_t* n_dev, int prec, float scale,
+                 float* out, nm_stream_t st) {
+    return lw ? nm_mlp_forward_listed_live(m, pts, dirs, n, idx, n_dev, n, prec, scale, out, lw->ws, lw->bytes, lw->chunk, st)
+              : nm_mlp_forward_listed(m, pts, dirs, n, idx, n_dev, n, prec, scale, out, st);
+}
 }  // namespace
+
+// what a *_live entry checks of its live workspace before anything is enqueued: a composited pass of n samples (S_ray to a ray) at precision prec
+#define NM_LIVE_WS_REQUIRE(who, prec, n, S_ray)                                                                                                     \
+    NM_REQUIRE((reinterpret_cast<uintptr_t>(live_ws) & 15) == 0, who ": live_ws must be 16-byte aligned");                                          \
+    NM_REQUIRE(chunk_samples <= 0 || chunk_samples >= (S_ray), who ": chunk_samples holds no whole ray of %d samples", (int)(S_ray));               \
+    NM_REQUIRE((prec) != NM_PREC_I8X3 || (n) <= 0 || (live_ws && live_ws_bytes >= nm_mlp_live_workspace_bytes(n, chunk_samples)),                   \
+               who ": live workspace of %lld bytes, %lld needed", (long long)live_ws_bytes, (long long)nm_mlp_live_workspace_bytes(n, chunk_samples))
 
 extern "C" {
 
@@ -16,18 +47,19 @@ int64_t nm_render_rays_bkg_workspace_floats(int64_t R, int S, int N) {
     return N > 0 ? align4(R * S) + align4(R * S * 4) + align4(R * S) + align4(R * 6) : align4(R * 6);
 }
 
-int nm_render_rays_bkg(nm_mlp_t coarse, nm_mlp_t fine, const float* origin, const float* direction, const float* near, const float* far,
-                       int64_t R, int S, int N, const float* t_vals, const float* u, int white_bkg, int precision_coarse, int precision_fine,
-                       float* workspace, float* raw_out, float* z_out, float* rgb, float* depth, float* acc, nm_stream_t stream) {
-    NM_REQUIRE(R == 0 || (coarse && origin && direction && near && far && t_vals && workspace && raw_out && z_out), "nm_render_rays_bkg: null pointer");
-    NM_REQUIRE(R >= 0 && S >= 1 && N >= 0 && (N == 0) == (fine == nullptr), "nm_render_rays_bkg: a fine net and N > 0 importance samples go together (S=%d N=%d)", S, N);
-    NM_REQUIRE(N == 0 || u, "nm_render_rays_bkg: u [N] is missing");
+static int render_rays_bkg(const LiveWs* lw, nm_mlp_t coarse, nm_mlp_t fine, const float* origin, const float* direction, const float* near, const float* far,
+                           int64_t R, int S, int N, const float* t_vals, const float* u, int white_bkg, int precision_coarse, int precision_fine,
+                           float* workspace, float* raw_out, float* z_out, float* rgb, float* depth, float* acc, nm_stream_t stream) {
+    const char* who = lw ? "nm_render_rays_bkg_live" : "nm_render_rays_bkg";       // (one body, two entries: errors name the one that was called)
+    NM_REQUIRE(R == 0 || (coarse && origin && direction && near && far && t_vals && workspace && raw_out && z_out), "%s: null pointer", who);
+    NM_REQUIRE(R >= 0 && S >= 1 && N >= 0 && (N == 0) == (fine == nullptr), "%s: a fine net and N > 0 importance samples go together (S=%d N=%d)", who, S, N);
+    NM_REQUIRE(N == 0 || u, "%s: u [N] is missing", who);
     if (R == 0) return NM_OK;
     int rc;
     float* scratch = workspace + (N > 0 ? align4(R * S) + align4(R * S * 4) + align4(R * S) : 0);      // [R,6]
     if (!fine) {                                                  // one pass: its output is what is composited
         if ((rc = nm_ray_to_samples(origin, direction, near, far, R, S, t_vals, 0, nullptr, nullptr, nullptr, z_out, stream))) return rc;
-        if ((rc = nm_mlp_forward_rays(coarse, origin, direction, z_out, R, S, precision_coarse, 1.f, raw_out, stream))) return rc;
+        if ((rc = shade_rays(lw, coarse, origin, direction, z_out, R, S, precision_coarse, 1.f, raw_out, stream))) return rc;
     } else {
         float* zc = workspace;
         float* rawc = zc + align4(R * S);
@@ -38,13 +70,31 @@ int nm_render_rays_bkg(nm_mlp_t coarse, nm_mlp_t fine, const float* origin, cons
         // (the coarse composite's colours are discarded, as the reference discards them, :139-141: ONE kernel from sigma to the samples)
         (void)wc;
         if ((rc = nm_importance_from_raw(rawc, zc, direction, R, S, u, N, z_out, nullptr, stream))) return rc;
-        if ((rc = nm_mlp_forward_rays(fine, origin, direction, z_out, R, S + N, precision_fine, 1.f, raw_out, stream))) return rc;
+        if ((rc = shade_rays(lw, fine, origin, direction, z_out, R, S + N, precision_fine, 1.f, raw_out, stream))) return rc;
     }
     if (rgb) {
-        NM_REQUIRE(depth && acc, "nm_render_rays_bkg: rgb, depth and acc go together");
+        NM_REQUIRE(depth && acc, "%s: rgb, depth and acc go together", who);
         if ((rc = nm_composite(raw_out, z_out, direction, R, S + N, white_bkg, nullptr, rgb, scratch + 3 * R, acc, nullptr, depth, stream))) return rc;
     }
     return NM_OK;
+}
+
+int nm_render_rays_bkg(nm_mlp_t coarse, nm_mlp_t fine, const float* origin, const float* direction, const float* near, const float* far,
+                       int64_t R, int S, int N, const float* t_vals, const float* u, int white_bkg, int precision_coarse, int precision_fine,
+                       float* workspace, float* raw_out, float* z_out, float* rgb, float* depth, float* acc, nm_stream_t stream) {
+    return render_rays_bkg(nullptr, coarse, fine, origin, direction, near, far, R, S, N, t_vals, u, white_bkg, precision_coarse, precision_fine, workspace, raw_out,
+                           z_out, rgb, depth, acc, stream);
+}
+
+int nm_render_rays_bkg_live(nm_mlp_t coarse, nm_mlp_t fine, const float* origin, const float* direction, const float* near, const float* far,
+                            int64_t R, int S, int N, const float* t_vals, const float* u, int white_bkg, int precision_coarse, int precision_fine,
+                            float* workspace, float* raw_out, float* z_out, float* rgb, float* depth, float* acc, void* live_ws, int64_t live_ws_bytes,
+                            int64_t chunk_samples, nm_stream_t stream) {
+    NM_REQUIRE(S >= 1 && N >= 0, "nm_render_rays_bkg_live: bad sizes");
+    NM_LIVE_WS_REQUIRE("nm_render_rays_bkg_live", fine ? precision_fine : precision_coarse, R * (int64_t)(S + N), S + N);
+    const LiveWs lw{live_ws, live_ws_bytes, chunk_samples};
+    return render_rays_bkg(&lw, coarse, fine, origin, direction, near, far, R, S, N, t_vals, u, white_bkg, precision_coarse, precision_fine, workspace, raw_out,
+                           z_out, rgb, depth, acc, stream);
 }
 
 int64_t nm_render_rays_human_workspace_floats(int64_t R, int S, int posed) {
@@ -52,30 +102,49 @@ int64_t nm_render_rays_human_workspace_floats(int64_t R, int S, int posed) {
     return (posed ? 3 * align4(R * S * 3) : 0) + align4(R);
 }
 
-int nm_render_rays_human(nm_mlp_t human, nm_mesh_t mesh, const double* T, const float* origin, const float* direction, const float* near,
-                         const float* far, int64_t R, int S, const float* t_vals, int white_bkg, float sigma_scale, int precision,
-                         float* workspace, float* raw_out, float* z_out, float* rgb, float* depth, float* acc, nm_stream_t stream) {
-    NM_REQUIRE(R == 0 || (human && origin && direction && near && far && t_vals && workspace && raw_out && z_out), "nm_render_rays_human: null pointer");
-    NM_REQUIRE(R >= 0 && S >= 1 && (mesh == nullptr) == (T == nullptr), "nm_render_rays_human: a posed mesh and its transforms go together");
+static int render_rays_human(const LiveWs* lw, nm_mlp_t human, nm_mesh_t mesh, const double* T, const float* origin, const float* direction, const float* near,
+                             const float* far, int64_t R, int S, const float* t_vals, int white_bkg, float sigma_scale, int precision,
+                             float* workspace, float* raw_out, float* z_out, float* rgb, float* depth, float* acc, nm_stream_t stream) {
+    const char* who = lw ? "nm_render_rays_human_live" : "nm_render_rays_human";       // (one body, two entries: errors name the one that was called)
+    NM_REQUIRE(R == 0 || (human && origin && direction && near && far && t_vals && workspace && raw_out && z_out), "%s: null pointer", who);
+    NM_REQUIRE(R >= 0 && S >= 1 && (mesh == nullptr) == (T == nullptr), "%s: a posed mesh and its transforms go together", who);
     if (R == 0) return NM_OK;
     int rc;
     float* disp = workspace + (mesh ? 3 * align4(R * S * 3) : 0);
     if (!mesh) {                                                  // canonical render (render_can=True, :213-216): the camera ray is the view direction
         if ((rc = nm_ray_to_samples(origin, direction, near, far, R, S, t_vals, 0, nullptr, nullptr, nullptr, z_out, stream))) return rc;
-        if ((rc = nm_mlp_forward_rays(human, origin, direction, z_out, R, S, precision, sigma_scale, raw_out, stream))) return rc;
+        if ((rc = shade_rays(lw, human, origin, direction, z_out, R, S, precision, sigma_scale, raw_out, stream))) return rc;
     } else {                                                      // posed: warp the samples, directions = differences of warped points (:217-227)
         float* pts = workspace;
         float* can_pts = pts + align4(R * S * 3);
         float* can_dirs = can_pts + align4(R * S * 3);
         if ((rc = nm_ray_to_samples(origin, direction, near, far, R, S, t_vals, 0, nullptr, pts, nullptr, z_out, stream))) return rc;
         if ((rc = nm_warp_to_canonical(mesh, pts, R, S, T, can_pts, can_dirs, nullptr, stream))) return rc;
-        if ((rc = nm_mlp_forward(human, can_pts, can_dirs, R * S, precision, sigma_scale, raw_out, stream))) return rc;
+        if ((rc = shade_points(lw, human, can_pts, can_dirs, R * S, precision, sigma_scale, raw_out, stream))) return rc;
     }
     if (rgb) {
-        NM_REQUIRE(depth && acc, "nm_render_rays_human: rgb, depth and acc go together");
+        NM_REQUIRE(depth && acc, "%s: rgb, depth and acc go together", who);
         if ((rc = nm_composite(raw_out, z_out, direction, R, S, white_bkg, nullptr, rgb, disp, acc, nullptr, depth, stream))) return rc;
     }
     return NM_OK;
+}
+
+int nm_render_rays_human(nm_mlp_t human, nm_mesh_t mesh, const double* T, const float* origin, const float* direction, const float* near,
+                         const float* far, int64_t R, int S, const float* t_vals, int white_bkg, float sigma_scale, int precision,
+                         float* workspace, float* raw_out, float* z_out, float* rgb, float* depth, float* acc, nm_stream_t stream) {
+    return render_rays_human(nullptr, human, mesh, T, origin, direction, near, far, R, S, t_vals, white_bkg, sigma_scale, precision, workspace, raw_out, z_out, rgb,
+                             depth, acc, stream);
+}
+
+int nm_render_rays_human_live(nm_mlp_t human, nm_mesh_t mesh, const double* T, const float* origin, const float* direction, const float* near,
+                              const float* far, int64_t R, int S, const float* t_vals, int white_bkg, float sigma_scale, int precision,
+                              float* workspace, float* raw_out, float* z_out, float* rgb, float* depth, float* acc, void* live_ws, int64_t live_ws_bytes,
+                              int64_t chunk_samples, nm_stream_t stream) {
+    NM_REQUIRE(S >= 1, "nm_render_rays_human_live: bad sizes");
+    NM_LIVE_WS_REQUIRE("nm_render_rays_human_live", precision, R * (int64_t)S, S);
+    const LiveWs lw{live_ws, live_ws_bytes, chunk_samples};
+    return render_rays_human(&lw, human, mesh, T, origin, direction, near, far, R, S, t_vals, white_bkg, sigma_scale, precision, workspace, raw_out, z_out, rgb,
+                             depth, acc, stream);
 }
 
 // K11b: the human pass with occupancy-grid empty-space skipping (occupancy.hip).  The workspace starts with nm_render_rays_human's layout
@@ -84,19 +153,20 @@ int64_t nm_render_rays_human_occ_workspace_floats(int64_t R, int S, int posed) {
     return nm_render_rays_human_workspace_floats(R, S, posed) + align4(R * S) + align4(nm_occ_compact_workspace_ints(R * S));
 }
 
-int nm_render_rays_human_occ(nm_mlp_t human, nm_mesh_t mesh, const double* T, const uint32_t* bits, int res, const float* aabb, const float* origin,
-                             const float* direction, const float* near, const float* far, int64_t R, int S, const float* t_vals, int white_bkg,
-                             float sigma_scale, int precision, float* workspace, float* raw_out, float* z_out, int32_t* counts, float* rgb, float* depth,
-                             float* acc, nm_stream_t stream) {
-    NM_REQUIRE(bits && aabb && counts, "nm_render_rays_human_occ: null pointer");
-    NM_REQUIRE(R == 0 || (human && origin && direction && near && far && t_vals && workspace && raw_out && z_out), "nm_render_rays_human_occ: null pointer");
-    NM_REQUIRE(R >= 0 && S >= 1 && (mesh == nullptr) == (T == nullptr), "nm_render_rays_human_occ: a posed mesh and its transforms go together");
-    NM_REQUIRE(R * (int64_t)S < (1ll << 31), "nm_render_rays_human_occ: too many samples (R=%lld S=%d)", (long long)R, S);
+static int render_rays_human_occ(const LiveWs* lw, nm_mlp_t human, nm_mesh_t mesh, const double* T, const uint32_t* bits, int res, const float* aabb,
+                                 const float* origin, const float* direction, const float* near, const float* far, int64_t R, int S, const float* t_vals,
+                                 int white_bkg, float sigma_scale, int precision, float* workspace, float* raw_out, float* z_out, int32_t* counts, float* rgb,
+                                 float* depth, float* acc, nm_stream_t stream) {
+    const char* who = lw ? "nm_render_rays_human_occ_live" : "nm_render_rays_human_occ";       // (one body, two entries: errors name the one that was called)
+    NM_REQUIRE(bits && aabb && counts, "%s: null pointer", who);
+    NM_REQUIRE(R == 0 || (human && origin && direction && near && far && t_vals && workspace && raw_out && z_out), "%s: null pointer", who);
+    NM_REQUIRE(R >= 0 && S >= 1 && (mesh == nullptr) == (T == nullptr), "%s: a posed mesh and its transforms go together", who);
+    NM_REQUIRE(R * (int64_t)S < (1ll << 31), "%s: too many samples (R=%lld S=%d)", who, (long long)R, S);
     hipStream_t st = nm::as_stream(stream);
     int rc;
-    if (R == 0) return nm::check_hip(hipMemsetAsync(counts, 0, 8, st), "nm_render_rays_human_occ: counts");
+    if (R == 0) return nm::check_hip(hipMemsetAsync(counts, 0, 8, st), (std::string(who) + ": counts").c_str());
     // a skipped sample keeps raw = 0: alpha 0, weight 0 -- what relu(sigma) = 0 gives
-    if ((rc = nm::check_hip(hipMemsetAsync(raw_out, 0, (size_t)(R * S) * 16, st), "nm_render_rays_human_occ: raw"))) return rc;
+    if ((rc = nm::check_hip(hipMemsetAsync(raw_out, 0, (size_t)(R * S) * 16, st), (std::string(who) + ": raw").c_str()))) return rc;
     const int64_t base = nm_render_rays_human_workspace_floats(R, S, mesh != nullptr);
     float* disp = workspace + (mesh ? 3 * align4(R * S * 3) : 0);
     int32_t* idx = reinterpret_cast<int32_t*>(workspace + base);
@@ -104,7 +174,7 @@ int nm_render_rays_human_occ(nm_mlp_t human, nm_mesh_t mesh, const double* T, co
     if (!mesh) {                                                  // canonical: the grid is tested on o + d z itself (in_mode 3)
         if ((rc = nm_ray_to_samples(origin, direction, near, far, R, S, t_vals, 0, nullptr, nullptr, nullptr, z_out, stream))) return rc;
         if ((rc = nm_occ_compact_samples(bits, res, aabb, origin, direction, z_out, R, S, idx, counts, cws, stream))) return rc;
-        if ((rc = nm_mlp_forward_samples(human, origin, direction, z_out, R, S, idx, counts, R * S, precision, sigma_scale, raw_out, stream))) return rc;
+        if ((rc = shade_samples(lw, human, origin, direction, z_out, R, S, idx, counts, precision, sigma_scale, raw_out, stream))) return rc;
     } else {                                                      // posed: the grid lives in canonical space -- tested on the WARPED points (in_mode 4)
         float* pts = workspace;
         float* can_pts = pts + align4(R * S * 3);
@@ -112,13 +182,32 @@ int nm_render_rays_human_occ(nm_mlp_t human, nm_mesh_t mesh, const double* T, co
         if ((rc = nm_ray_to_samples(origin, direction, near, far, R, S, t_vals, 0, nullptr, pts, nullptr, z_out, stream))) return rc;
         if ((rc = nm_warp_to_canonical(mesh, pts, R, S, T, can_pts, can_dirs, nullptr, stream))) return rc;
         if ((rc = nm_occ_compact_points(bits, res, aabb, can_pts, R * S, idx, counts, cws, stream))) return rc;
-        if ((rc = nm_mlp_forward_listed(human, can_pts, can_dirs, R * S, idx, counts, R * S, precision, sigma_scale, raw_out, stream))) return rc;
+        if ((rc = shade_listed(lw, human, can_pts, can_dirs, R * S, idx, counts, precision, sigma_scale, raw_out, stream))) return rc;
     }
     if (rgb) {
-        NM_REQUIRE(depth && acc, "nm_render_rays_human_occ: rgb, depth and acc go together");
+        NM_REQUIRE(depth && acc, "%s: rgb, depth and acc go together", who);
         if ((rc = nm_composite(raw_out, z_out, direction, R, S, white_bkg, nullptr, rgb, disp, acc, nullptr, depth, stream))) return rc;
     }
     return NM_OK;
+}
+
+int nm_render_rays_human_occ(nm_mlp_t human, nm_mesh_t mesh, const double* T, const uint32_t* bits, int res, const float* aabb, const float* origin,
+                             const float* direction, const float* near, const float* far, int64_t R, int S, const float* t_vals, int white_bkg,
+                             float sigma_scale, int precision, float* workspace, float* raw_out, float* z_out, int32_t* counts, float* rgb, float* depth,
+                             float* acc, nm_stream_t stream) {
+    return render_rays_human_occ(nullptr, human, mesh, T, bits, res, aabb, origin, direction, near, far, R, S, t_vals, white_bkg, sigma_scale, precision, workspace,
+                                 raw_out, z_out, counts, rgb, depth, acc, stream);
+}
+
+int nm_render_rays_human_occ_live(nm_mlp_t human, nm_mesh_t mesh, const double* T, const uint32_t* bits, int res, const float* aabb, const float* origin,
+                                  const float* direction, const float* near, const float* far, int64_t R, int S, const float* t_vals, int white_bkg,
+                                  float sigma_scale, int precision, float* workspace, float* raw_out, float* z_out, int32_t* counts, float* rgb, float* depth,
+                                  float* acc, void* live_ws, int64_t live_ws_bytes, int64_t chunk_samples, nm_stream_t stream) {
+    NM_REQUIRE(S >= 1, "nm_render_rays_human_occ_live: bad sizes");
+    NM_LIVE_WS_REQUIRE("nm_render_rays_human_occ_live", precision, R * (int64_t)S, S);
+    const LiveWs lw{live_ws, live_ws_bytes, chunk_samples};
+    return render_rays_human_occ(&lw, human, mesh, T, bits, res, aabb, origin, direction, near, far, R, S, t_vals, white_bkg, sigma_scale, precision, workspace,
+                                 raw_out, z_out, counts, rgb, depth, acc, stream);
 }
 
 // (the merged list lives in LDS now: nothing is needed; kept for callers that size a workspace)
@@ -171,38 +260,39 @@ inline HybridWs hybrid_layout(float* base, int64_t R, int S, int N, int Sh) {
 
 int64_t nm_render_rays_hybrid_workspace_floats(int64_t R, int S, int N, int S_human) { return hybrid_layout(nullptr, R, S, N, S_human).total; }
 
-int nm_render_rays_hybrid(nm_mlp_t coarse, nm_mlp_t fine, nm_mlp_t human, nm_mesh_t mesh, const double* T, const float* verts, int V,
-                          double geo_threshold, const float* origin, const float* direction, int64_t R, float bkg_near, float bkg_far, int S, int N,
-                          int S_human, const float* t_vals, const float* u, const float* t_vals_human, int white_bkg, int precision_coarse,
-                          int precision_fine, int precision_human, float* workspace, float* rgb, float* depth, float* acc, nm_stream_t stream) {
+static int render_rays_hybrid(const LiveWs* lw, nm_mlp_t coarse, nm_mlp_t fine, nm_mlp_t human, nm_mesh_t mesh, const double* T, const float* verts, int V,
+                              double geo_threshold, const float* origin, const float* direction, int64_t R, float bkg_near, float bkg_far, int S, int N,
+                              int S_human, const float* t_vals, const float* u, const float* t_vals_human, int white_bkg, int precision_coarse,
+                              int precision_fine, int precision_human, float* workspace, float* rgb, float* depth, float* acc, nm_stream_t stream) {
+    const char* who = lw ? "nm_render_rays_hybrid_live" : "nm_render_rays_hybrid";       // (one body, two entries: errors name the one that was called)
     NM_REQUIRE(R == 0 || (coarse && human && mesh && T && verts && origin && direction && t_vals && t_vals_human && workspace && rgb && depth && acc),
-               "nm_render_rays_hybrid: null pointer");
-    NM_REQUIRE(R >= 0 && S >= 1 && N >= 0 && S_human >= 2 && V >= 1, "nm_render_rays_hybrid: bad sizes");
+               "%s: null pointer", who);
+    NM_REQUIRE(R >= 0 && S >= 1 && N >= 0 && S_human >= 2 && V >= 1, "%s: bad sizes", who);
     if (R == 0) return NM_OK;
     hipStream_t st = nm::as_stream(stream);
     const HybridWs w = hybrid_layout(workspace, R, S, N, S_human);
     const int Sb = S + N;
     int rc;
     union { float f; uint32_t u; } nb{bkg_near}, fb{bkg_far};
-    if ((rc = nm::check_hip(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w.near_b), (int)nb.u, (size_t)R, st), "nm_render_rays_hybrid: near"))) return rc;
-    if ((rc = nm::check_hip(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w.far_b), (int)fb.u, (size_t)R, st), "nm_render_rays_hybrid: far"))) return rc;
+    if ((rc = nm::check_hip(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w.near_b), (int)nb.u, (size_t)R, st), (std::string(who) + ": near").c_str()))) return rc;
+    if ((rc = nm::check_hip(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w.far_b), (int)fb.u, (size_t)R, st), (std::string(who) + ": far").c_str()))) return rc;
     // every ray: the background-only composite; acc is forced to 0 where the body is missed (:311)
-    if ((rc = nm_render_rays_bkg(coarse, fine, origin, direction, w.near_b, w.far_b, R, S, N, t_vals, u, white_bkg, precision_coarse, precision_fine, w.bkg_ws,
-                                 w.raw_b, w.z_b, rgb, depth, acc, stream))) return rc;
-    if ((rc = nm::check_hip(hipMemsetAsync(acc, 0, (size_t)R * 4, st), "nm_render_rays_hybrid: acc"))) return rc;
+    if ((rc = render_rays_bkg(lw, coarse, fine, origin, direction, w.near_b, w.far_b, R, S, N, t_vals, u, white_bkg, precision_coarse, precision_fine, w.bkg_ws,
+                              w.raw_b, w.z_b, rgb, depth, acc, stream))) return rc;
+    if ((rc = nm::check_hip(hipMemsetAsync(acc, 0, (size_t)R * 4, st), (std::string(who) + ": acc").c_str()))) return rc;
     if ((rc = nm_near_far(origin, direction, R, verts, V, geo_threshold, w.near_h, w.far_h, stream))) return rc;
     if ((rc = nm_compact_hits(w.near_h, w.far_h, R, w.hit, nullptr, w.counts, w.cws, stream))) return rc;
     int32_t n_hit = 0;
-    if ((rc = nm::check_hip(hipMemcpyAsync(&n_hit, w.counts, 4, hipMemcpyDeviceToHost, st), "nm_render_rays_hybrid: hit count"))) return rc;
-    if ((rc = nm::check_hip(hipStreamSynchronize(st), "nm_render_rays_hybrid: hit count"))) return rc;
+    if ((rc = nm::check_hip(hipMemcpyAsync(&n_hit, w.counts, 4, hipMemcpyDeviceToHost, st), (std::string(who) + ": hit count").c_str()))) return rc;
+    if ((rc = nm::check_hip(hipStreamSynchronize(st), (std::string(who) + ": hit count").c_str()))) return rc;
     if (n_hit == 0) return NM_OK;
     // the hit rays: overwritten by the merged human + background composite (:313-353)
     if ((rc = nm_gather_rows(origin, w.hit, nullptr, n_hit, 3, w.ho, stream))) return rc;
     if ((rc = nm_gather_rows(direction, w.hit, nullptr, n_hit, 3, w.hd, stream))) return rc;
     if ((rc = nm_gather_rows(w.near_h, w.hit, nullptr, n_hit, 1, w.hn, stream))) return rc;
     if ((rc = nm_gather_rows(w.far_h, w.hit, nullptr, n_hit, 1, w.hf, stream))) return rc;
-    if ((rc = nm_render_rays_human(human, mesh, T, w.ho, w.hd, w.hn, w.hf, n_hit, S_human, t_vals_human, white_bkg, 1.f, precision_human, w.human_ws, w.h_raw,
-                                   w.h_z, nullptr, nullptr, nullptr, stream))) return rc;
+    if ((rc = render_rays_human(lw, human, mesh, T, w.ho, w.hd, w.hn, w.hf, n_hit, S_human, t_vals_human, white_bkg, 1.f, precision_human, w.human_ws, w.h_raw,
+                                w.h_z, nullptr, nullptr, nullptr, stream))) return rc;
     {                                                                 // merged composite: the background lists of the hit rays read in place
         const float* zs[2] = {w.z_b, w.h_z};
         const float* raws[2] = {w.raw_b, w.h_raw};
@@ -215,6 +305,27 @@ int nm_render_rays_hybrid(nm_mlp_t coarse, nm_mlp_t fine, nm_mlp_t human, nm_mes
     if ((rc = nm_scatter_rows(w.rgb_h, w.hit, nullptr, n_hit, 3, rgb, stream))) return rc;
     if ((rc = nm_scatter_rows(w.depth_h, w.hit, nullptr, n_hit, 1, depth, stream))) return rc;
     return nm_scatter_rows(w.acc_h, w.hit, nullptr, n_hit, 1, acc, stream);
+}
+
+int nm_render_rays_hybrid(nm_mlp_t coarse, nm_mlp_t fine, nm_mlp_t human, nm_mesh_t mesh, const double* T, const float* verts, int V,
+                          double geo_threshold, const float* origin, const float* direction, int64_t R, float bkg_near, float bkg_far, int S, int N,
+                          int S_human, const float* t_vals, const float* u, const float* t_vals_human, int white_bkg, int precision_coarse,
+                          int precision_fine, int precision_human, float* workspace, float* rgb, float* depth, float* acc, nm_stream_t stream) {
+    return render_rays_hybrid(nullptr, coarse, fine, human, mesh, T, verts, V, geo_threshold, origin, direction, R, bkg_near, bkg_far, S, N, S_human, t_vals, u,
+                              t_vals_human, white_bkg, precision_coarse, precision_fine, precision_human, workspace, rgb, depth, acc, stream);
+}
+
+int nm_render_rays_hybrid_live(nm_mlp_t coarse, nm_mlp_t fine, nm_mlp_t human, nm_mesh_t mesh, const double* T, const float* verts, int V,
+                               double geo_threshold, const float* origin, const float* direction, int64_t R, float bkg_near, float bkg_far, int S, int N,
+                               int S_human, const float* t_vals, const float* u, const float* t_vals_human, int white_bkg, int precision_coarse,
+                               int precision_fine, int precision_human, float* workspace, float* rgb, float* depth, float* acc, void* live_ws,
+                               int64_t live_ws_bytes, int64_t chunk_samples, nm_stream_t stream) {
+    NM_REQUIRE(S >= 1 && N >= 0 && S_human >= 2, "nm_render_rays_hybrid_live: bad sizes");
+    NM_LIVE_WS_REQUIRE("nm_render_rays_hybrid_live", fine ? precision_fine : precision_coarse, R * (int64_t)(S + N), S + N);      // the two composited passes
+    NM_LIVE_WS_REQUIRE("nm_render_rays_hybrid_live", precision_human, R * (int64_t)S_human, S_human);                              // share live_ws
+    const LiveWs lw{live_ws, live_ws_bytes, chunk_samples};
+    return render_rays_hybrid(&lw, coarse, fine, human, mesh, T, verts, V, geo_threshold, origin, direction, R, bkg_near, bkg_far, S, N, S_human, t_vals, u,
+                              t_vals_human, white_bkg, precision_coarse, precision_fine, precision_human, workspace, rgb, depth, acc, stream);
 }
 
 }  // extern "C"

@@ -83,6 +83,14 @@ SIGNATURES = {
     "nm_mlp_forward_rays_live_workspace_bytes": (i64, [i64, i32, i64]),
     "nm_mlp_forward_rays_live": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, i32, ctypes.c_float, c_f32p, ctypes.c_void_p, i64, i64, c_stream]),
     "nm_mlp_sigma_rays": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, i32, ctypes.c_float, c_f32p, c_stream]),
+    "nm_mlp_live_workspace_bytes": (i64, [i64, i64]),
+    "nm_mlp_forward_live": (i32, [ctypes.c_void_p, c_f32p, c_f32p, i64, i32, ctypes.c_float, c_f32p, ctypes.c_void_p, i64, i64, c_stream]),
+    "nm_mlp_forward_listed_live": (i32, [ctypes.c_void_p, c_f32p, c_f32p, i64, c_i32p, c_i32p, i64, i32, ctypes.c_float, c_f32p, ctypes.c_void_p, i64, i64,
+                                         c_stream]),
+    "nm_mlp_forward_samples_live": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, c_i32p, c_i32p, i64, i32, ctypes.c_float, c_f32p, ctypes.c_void_p,
+                                          i64, i64, c_stream]),
+    "nm_mlp_forward_ray_chunk_live": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i32, c_i32p, c_i32p, i64, i32, i32, i32, ctypes.c_float, c_f32p,
+                                            ctypes.c_void_p, i64, i64, c_stream]),
     "nm_mlp_forward_ray_chunk": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i32, c_i32p, c_i32p, i64, i32, i32, i32, ctypes.c_float, c_f32p,
                                        c_stream]),
     "nm_mlp_sigma_ray_chunk": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i32, c_i32p, c_i32p, i64, i32, i32, i32, ctypes.c_float, c_f32p,
@@ -147,6 +155,16 @@ SIGNATURES = {
     "nm_render_rays_hybrid": (i32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_f32p, i32, ctypes.c_double, c_f32p, c_f32p,
                                     i64, ctypes.c_float, ctypes.c_float, i32, i32, i32, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, c_f32p, c_f32p, c_f32p, c_f32p,
                                     c_stream]),
+    "nm_render_rays_bkg_live": (i32, [ctypes.c_void_p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, i64, i32, i32, c_f32p, c_f32p, i32, i32, i32, c_f32p, c_f32p,
+                                      c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, i64, i64, c_stream]),
+    "nm_render_rays_human_live": (i32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, i64, i32, c_f32p, i32, ctypes.c_float,
+                                        i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, i64, i64, c_stream]),
+    "nm_render_rays_human_occ_live": (i32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_i32p, i32, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, i64,
+                                            i32, c_f32p, i32, ctypes.c_float, i32, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, i64,
+                                            i64, c_stream]),
+    "nm_render_rays_hybrid_live": (i32, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_f32p, i32, ctypes.c_double, c_f32p,
+                                         c_f32p, i64, ctypes.c_float, ctypes.c_float, i32, i32, i32, c_f32p, c_f32p, c_f32p, i32, i32, i32, i32, c_f32p, c_f32p,
+                                         c_f32p, c_f32p, ctypes.c_void_p, i64, i64, c_stream]),
     "nm_merge_composite_lists": (i32, [i32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                        ctypes.POINTER(ctypes.c_int), i64, c_f32p, i32, c_f32p, c_f32p, c_f32p, c_stream]),
     "nm_merged_intervals": (i32, [i32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int), i64, ctypes.POINTER(ctypes.c_void_p), c_stream]),

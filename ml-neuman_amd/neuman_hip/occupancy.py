@@ -20,6 +20,10 @@ nm_occ_compact_points).  The fused hybrid call gives way to the unfused passes w
     grid = OccupancyGrid.from_net(human.coarse_human_net, canonical_aabb(static_verts, 0.1))
     attach(human.coarse_human_net, grid)
 
+A gridded pass whose raw is composited and nothing else (role='composite': render_utils.LIVE_HEADS and the composite-only rule there) also
+leaves the colour head to the evaluated samples that have density: forward_rays / forward_points run nm_mlp_forward_samples_live /
+nm_mlp_forward_listed_live, the fused human pass nm_render_rays_human_occ_live; the frame is bit-identical.
+
 Training never consults a grid: the trainers evaluate their nets through the training forward (Joiner.forward in train() mode,
 neuman_hip/train.py) on the points of the batch, which knows nothing of grids -- a human-trainer step is the same with or without
 one (tests/test_hip_occupancy_human.py).  Rebuild the grid (from_net) after training has moved the density.
@@ -224,9 +228,10 @@ def grid_of(net):
     return getattr(net, _ATTR, None) if net is not None else None
 
 
-def forward_rays(net, o, d, z, precision=None, role=None, sigma_only=False, stats=None):
+def forward_rays(net, o, d, z, precision=None, role=None, sigma_only=False, stats=None, chunk_samples=0):
     """net.forward_rays over the grid's occupied samples only: raw [R,S,4], zero on every skipped sample.  `stats` (a dict)
-    receives 'evaluated' / 'total' sample counts (one host read)."""
+    receives 'evaluated' / 'total' sample counts (one host read).  role='composite': as Joiner.forward_rays -- the colour head runs on the
+    evaluated samples with density only (nm_mlp_forward_samples_live, in pieces of `chunk_samples`; Joiner.live_route says when)."""
     grid = grid_of(net)
     net._guard(o, d, z)
     o, d, z = o.contiguous(), d.contiguous(), z.contiguous()
@@ -236,19 +241,28 @@ def forward_rays(net, o, d, z, precision=None, role=None, sigma_only=False, stat
         return raw
     idx, counts = grid.compact(o, d, z)
     L = _lib.lib()
-    entry = L.nm_mlp_sigma_samples if sigma_only else L.nm_mlp_forward_samples
-    _lib.check(entry(net.handle(), _lib.dev_ptr(o, name='origin'), _lib.dev_ptr(d, name='direction'), _lib.dev_ptr(z, name='z_vals'), R, S,
-                     _lib.dev_ptr(idx, torch.int32), _lib.dev_ptr(counts, torch.int32), R * S, net._prec(precision, role), 1.0,
-                     _lib.dev_ptr(raw), _lib.stream_ptr()), "nm_mlp_sigma_samples" if sigma_only else "nm_mlp_forward_samples")
+    if net.live_route(precision, role, R * S, sigma_only):
+        from .vanilla import live_workspace_for
+        ws, nbytes = live_workspace_for(R * S, chunk_samples, z.device)
+        _lib.check(L.nm_mlp_forward_samples_live(net.handle(), _lib.dev_ptr(o, name='origin'), _lib.dev_ptr(d, name='direction'), _lib.dev_ptr(z, name='z_vals'),
+                                                 R, S, _lib.dev_ptr(idx, torch.int32), _lib.dev_ptr(counts, torch.int32), R * S, net._prec(precision, role), 1.0,
+                                                 _lib.dev_ptr(raw), _lib.dev_ptr(ws, torch.uint8), nbytes, int(chunk_samples), _lib.stream_ptr()),
+                   "nm_mlp_forward_samples_live")
+    else:
+        entry = L.nm_mlp_sigma_samples if sigma_only else L.nm_mlp_forward_samples
+        _lib.check(entry(net.handle(), _lib.dev_ptr(o, name='origin'), _lib.dev_ptr(d, name='direction'), _lib.dev_ptr(z, name='z_vals'), R, S,
+                         _lib.dev_ptr(idx, torch.int32), _lib.dev_ptr(counts, torch.int32), R * S, net._prec(precision, role), 1.0,
+                         _lib.dev_ptr(raw), _lib.stream_ptr()), "nm_mlp_sigma_samples" if sigma_only else "nm_mlp_forward_samples")
     if stats is not None:
         stats['evaluated'] = stats.get('evaluated', 0) + int(counts[0].item())
         stats['total'] = stats.get('total', 0) + R * S
     return raw
 
 
-def forward_points(net, pts, dirs, precision=None, sigma_scale=1.0, role=None, stats=None):
+def forward_points(net, pts, dirs, precision=None, sigma_scale=1.0, role=None, stats=None, chunk_samples=0):
     """net(pts, dirs) on the points its grid keeps only (nm_occ_compact_points + nm_mlp_forward_listed): [..., 4], zero on every skipped
-    point.  `stats` (a dict) receives 'evaluated' / 'total' point counts (one host read)."""
+    point.  `stats` (a dict) receives 'evaluated' / 'total' point counts (one host read).  role='composite': as forward_rays
+    (nm_mlp_forward_listed_live)."""
     grid = grid_of(net)
     net._guard(pts, dirs)
     shp = pts.shape[:-1]
@@ -259,9 +273,17 @@ def forward_points(net, pts, dirs, precision=None, sigma_scale=1.0, role=None, s
     if n == 0:
         return out.reshape(*shp, 4)
     idx, counts = grid.compact_points(p)
-    _lib.check(_lib.lib().nm_mlp_forward_listed(net.handle(), _lib.dev_ptr(p, name='pts'), _lib.dev_ptr(d, name='dirs'), n, _lib.dev_ptr(idx, torch.int32),
-                                                _lib.dev_ptr(counts, torch.int32), n, net._prec(precision, role), float(sigma_scale), _lib.dev_ptr(out),
-                                                _lib.stream_ptr()), "nm_mlp_forward_listed")
+    if net.live_route(precision, role, n):
+        from .vanilla import live_workspace_for
+        ws, nbytes = live_workspace_for(n, chunk_samples, p.device)
+        _lib.check(_lib.lib().nm_mlp_forward_listed_live(net.handle(), _lib.dev_ptr(p, name='pts'), _lib.dev_ptr(d, name='dirs'), n, _lib.dev_ptr(idx, torch.int32),
+                                                         _lib.dev_ptr(counts, torch.int32), n, net._prec(precision, role), float(sigma_scale), _lib.dev_ptr(out),
+                                                         _lib.dev_ptr(ws, torch.uint8), nbytes, int(chunk_samples), _lib.stream_ptr()),
+                   "nm_mlp_forward_listed_live")
+    else:
+        _lib.check(_lib.lib().nm_mlp_forward_listed(net.handle(), _lib.dev_ptr(p, name='pts'), _lib.dev_ptr(d, name='dirs'), n, _lib.dev_ptr(idx, torch.int32),
+                                                    _lib.dev_ptr(counts, torch.int32), n, net._prec(precision, role), float(sigma_scale), _lib.dev_ptr(out),
+                                                    _lib.stream_ptr()), "nm_mlp_forward_listed")
     if stats is not None:
         stats['evaluated'] = stats.get('evaluated', 0) + int(counts[0].item())
         stats['total'] = stats.get('total', 0) + n

@@ -14,13 +14,14 @@ its four frame renderers.  What differs is the execution plan:
 The `*_rays` functions work on device tensors (what bench.py and the multi-GPU path call); the reference
 named functions wrap them with ray generation and the final download.
 """
+import contextlib
 import ctypes
 import os
 
 import numpy as np
 import torch
 
-from . import _lib, occupancy, parallel, ray_utils
+from . import _lib, occupancy, parallel, ray_utils, vanilla
 from .ray_utils import DEFAULT_GEO_THRESH
 
 MAX_RAYS_PER_LAUNCH = int(os.environ.get("NEUMAN_MAX_RAYS_PER_LAUNCH", 1 << 20))
@@ -37,6 +38,38 @@ TERMINATION_CHUNK = int(os.environ.get("NEUMAN_TERMINATION_CHUNK", "32"))
 TERMINATION_COARSE = float(os.environ.get("NEUMAN_TERMINATION_COARSE", "4e-13"))
 TERMINATION_MIN_CHUNK = 16
 FUSED_HYBRID_RAYS = int(os.environ.get("NEUMAN_FUSED_HYBRID_RAYS", 1 << 17))
+# The colour head on live samples only (vanilla.Joiner role='composite': nm_mlp_forward_*_live, nm_render_rays_*_live) in every composited pass
+# of render_smpl_nerf, render_hybrid_nerf and render_hybrid_nerf_multi_persons, and in render_vanilla's gridded, marched and single-net passes.
+# Off: those passes run the whole network on every sample they evaluate (frames are bit-identical either way).  render_vanilla's plain path takes
+# the route whatever this says.
+#
+# The composite-only rule.  A pass may take the live route only when its `raw` reaches nothing but raw2outputs, merge_composite,
+# merge_composite_lists, merge_sorted followed by raw2outputs, transmittance_of, or nm_transmittance_chunk*.  These read a colour only as
+# weight x sigmoid(colour).  The weight is exactly 0 for any interval, merged ones included, when the stored density is <= 0.
+#
+# Off by default: the routes are bit-exact and tested, but their frame times on configs 3-5 have not been measured yet, and the rule of
+# profiles/live_heads.md admits a route as a default only on a measured gain (profiles/live_heads_all_passes.md).  NEUMAN_LIVE_HEADS=1 turns them on.
+LIVE_HEADS = os.environ.get("NEUMAN_LIVE_HEADS", "0") == "1"
+_RAW_COMPOSITED_ONLY = False                     # set by the renderers around their bodies (raw_composited_only); read by human_pass_rays / human_march_rays
+
+
+@contextlib.contextmanager
+def raw_composited_only(n_max, device):
+    """Inside the block the `raw` of human_pass_rays and human_march_rays is used under the composite-only rule above (a renderer's body), so
+    they may take the live route; called directly they return whole-network records.  n_max: the samples of the largest composited pass of
+    the block -- ONE live workspace serves them all (vanilla.live_workspace: allocated at the first live pass)."""
+    global _RAW_COMPOSITED_ONLY
+    prev = _RAW_COMPOSITED_ONLY
+    _RAW_COMPOSITED_ONLY = True
+    try:
+        with vanilla.live_workspace(n_max, device):
+            yield
+    finally:
+        _RAW_COMPOSITED_ONLY = prev
+
+
+def _human_role():
+    return 'composite' if LIVE_HEADS and _RAW_COMPOSITED_ONLY else 'shading'
 
 
 # ------------------------------------------------------------------------------------------------
@@ -215,7 +248,8 @@ def human_march_rays(human_net, o, d, near, far, samples_per_ray, mesh, eps, sig
     the merged list's transmittance can only be lower than that (the foreign samples' own factors are <= 1 + 1e-10), and what is skipped
     weighs < eps in the composite.  Without `dz` (render_smpl_nerf: the list is composited alone) the list's own intervals.  Every
     evaluated sample is bit-identical to human_pass_rays' (per-sample arithmetic; tests/test_hip_march.py).  With an occupancy grid on the
-    net (occupancy.attach, K11b) a chunk evaluates only its occupied canonical points; the others keep raw = 0."""
+    net (occupancy.attach, K11b) a chunk evaluates only its occupied canonical points; the others keep raw = 0.  Inside a renderer's body
+    (raw_composited_only) with LIVE_HEADS the colour of an evaluated sample whose density is <= 0 is 0 (role='composite')."""
     _lib.require_gpu()
     R, S = o.shape[0], int(samples_per_ray)
     dev = o.device
@@ -236,11 +270,11 @@ def human_march_rays(human_net, o, d, near, far, samples_per_ray, mesh, eps, sig
         k = s0 - a
         if grid is None:
             out = human_net(can_pts[:, k:k + c].contiguous(), can_dirs[:, k:k + c].contiguous(), precision=precision, sigma_scale=sigma_scale,
-                            role='shading')
+                            role=_human_role())
             evaluated += live.numel() * c
         else:                                                                       # the chunk's occupied canonical points only (K11b)
             out = occupancy.forward_points(human_net, can_pts[:, k:k + c].contiguous(), can_dirs[:, k:k + c].contiguous(), precision=precision,
-                                           sigma_scale=sigma_scale, role='shading', stats=occ_stats)
+                                           sigma_scale=sigma_scale, role=_human_role(), stats=occ_stats)
         raw[live, s0:s0 + c] = out
         launches += 1
         s0 += c
@@ -322,22 +356,25 @@ def _occupancy_pass(net, o, d, z, precision, role, sigma_only, trace, key):
     return raw
 
 
-def bkg_place_z(coarse_net, fine_net, o, d, near, far, samples_per_ray, importance_samples_per_ray, white_bkg, precision=None, trace=None):
+def bkg_place_z(coarse_net, fine_net, o, d, near, far, samples_per_ray, importance_samples_per_ray, white_bkg, precision=None, trace=None,
+                composite_only=False):
     """Where the background list's FINAL samples are (render_utils.py:131-147, 287-293): the stratified samples, or -- with a fine net --
     the coarse density pass, its compositing weights and the importance samples merged in.  -> (z [R,S'], raw of the coarse pass when it
-    is the pass that is composited [no fine net; evaluated here unless termination is on], else None)"""
+    is the pass that is composited [no fine net; evaluated here unless termination is on], else None).  composite_only: as bkg_shade, for that
+    raw (the single-net pass, gridded or whole)"""
+    role = 'composite' if composite_only and LIVE_HEADS else 'shading'
     occ = _occupancy_on(coarse_net)
     _, _, z = ray_utils.sample_z(o, d, near, far, samples_per_ray)
     if occ:
         # empty-space skipping (occupancy.py): skipped samples keep raw = 0 -- weight 0, as relu(sigma) = 0 gives
         if fine_net is None:
-            return z, _occupancy_pass(coarse_net, o, d, z, precision, 'shading', False, trace, 'occupancy_coarse')
+            return z, _occupancy_pass(coarse_net, o, d, z, precision, role, False, trace, 'occupancy_coarse')
         raw = _occupancy_pass(coarse_net, o, d, z, precision, None, True, trace, 'occupancy_coarse')
         z_fine, w = ray_utils.importance_z_from_raw(raw, z, d, importance_samples_per_ray, want_weights=trace is not None)
         _note(trace, coarse_z=z, coarse_w=w)
         return z_fine, None
     if fine_net is None:
-        return z, (None if TERMINATION_EPS > 0 else coarse_net.forward_rays(o, d, z, precision=precision, role='shading'))
+        return z, (None if TERMINATION_EPS > 0 else coarse_net.forward_rays(o, d, z, precision=precision, role=role))
     # with a fine net the coarse pass only places the importance samples (only its density is used, render_utils.py:139-141: the
     # colour head is skipped) and is not the pass the mixed precision policy tags 'shading' (vanilla.Joiner._prec)
     if TERMINATION_EPS > 0:
@@ -358,12 +395,13 @@ def bkg_shade(net, o, d, z, precision=None, trace=None, occluder=None, dz=None, 
     """The background pass that is composited, on its final samples (render_utils.py:148-151, 294-297): whole, or -- TERMINATION_EPS > 0 --
     marched front to back at eps (`occluder`, `dz`: march_pass_rays), or -- a grid attached (occupancy.attach) -- on its occupied samples.
     composite_only: the caller feeds the raw to raw2outputs and to nothing else, so the whole pass may leave the colour of a sample without
-    density at 0 (Joiner.forward_rays role='composite': its weight is exactly 0)"""
+    density at 0 (Joiner.forward_rays role='composite': its weight is exactly 0); with LIVE_HEADS so may the marched and the gridded pass"""
+    role = 'composite' if composite_only and LIVE_HEADS else 'shading'
     if _occupancy_on(net):
-        return _occupancy_pass(net, o, d, z, precision, 'shading', False, trace, 'occupancy')
+        return _occupancy_pass(net, o, d, z, precision, role, False, trace, 'occupancy')
     if TERMINATION_EPS > 0:
         stats = {} if trace is not None else None
-        raw = march_pass_rays(net, o, d, z, TERMINATION_EPS, precision=precision, stats=stats, occluder=occluder, dz=dz)
+        raw = march_pass_rays(net, o, d, z, TERMINATION_EPS, precision=precision, role=role, stats=stats, occluder=occluder, dz=dz)
         _note(trace, march=stats)
         return raw
     return net.forward_rays(o, d, z, precision=precision, role='composite' if composite_only else 'shading')
@@ -385,7 +423,8 @@ def bkg_pass_rays(coarse_net, fine_net, o, d, near, far, samples_per_ray, import
         z = given_z.to(torch.float32).contiguous()
         _note(trace, bkg_z=z)
         return net.forward_rays(o, d, z, precision=precision, role='shading'), z
-    z, raw = bkg_place_z(coarse_net, fine_net, o, d, near, far, samples_per_ray, importance_samples_per_ray, white_bkg, precision, trace)
+    z, raw = bkg_place_z(coarse_net, fine_net, o, d, near, far, samples_per_ray, importance_samples_per_ray, white_bkg, precision, trace,
+                         composite_only)
     if raw is None:
         raw = bkg_shade(net, o, d, z, precision, trace, occluder, dz, composite_only)
     _note(trace, bkg_z=z)
@@ -398,13 +437,15 @@ def render_vanilla_rays(coarse_net, fine_net, o, d, near, far, samples_per_ray, 
     R = o.shape[0]
     rgb = torch.empty((R, 3), device=o.device, dtype=torch.float32)
     depth = torch.empty(R, device=o.device, dtype=torch.float32)
-    for i, j in _chunks(R):
-        oc, dc = o[i:j], d[i:j]
-        n = torch.full((j - i,), float(near), device=o.device, dtype=torch.float32)
-        f = torch.full((j - i,), float(far), device=o.device, dtype=torch.float32)
-        raw, z = bkg_pass_rays(coarse_net, fine_net, oc, dc, n, f, samples_per_ray, importance_samples_per_ray, white_bkg,
-                               precision, trace, given['bkg_z'][i:j] if given is not None and 'bkg_z' in given else None, composite_only=True)
-        rgb[i:j], _, _, _, depth[i:j] = raw2outputs(raw, z, dc, white_bkg=white_bkg, want_weights=False)
+    S_max = int(samples_per_ray) + (int(importance_samples_per_ray) if fine_net is not None else 0)
+    with vanilla.live_workspace(min(R, MAX_RAYS_PER_LAUNCH) * S_max, o.device):                 # one live workspace for every pass and chunk of the call
+        for i, j in _chunks(R):
+            oc, dc = o[i:j], d[i:j]
+            n = torch.full((j - i,), float(near), device=o.device, dtype=torch.float32)
+            f = torch.full((j - i,), float(far), device=o.device, dtype=torch.float32)
+            raw, z = bkg_pass_rays(coarse_net, fine_net, oc, dc, n, f, samples_per_ray, importance_samples_per_ray, white_bkg,
+                                   precision, trace, given['bkg_z'][i:j] if given is not None and 'bkg_z' in given else None, composite_only=True)
+            rgb[i:j], _, _, _, depth[i:j] = raw2outputs(raw, z, dc, white_bkg=white_bkg, want_weights=False)
     return rgb, depth
 
 
@@ -421,25 +462,31 @@ def human_pass_rays(human_net, o, d, near, far, samples_per_ray, mesh=None, rend
     raw = torch.empty((R, S, 4), device=dev, dtype=torch.float32)
     z = torch.empty((R, S), device=dev, dtype=torch.float32)
     t_vals = torch.linspace(0., 1., steps=S, device=dev)
+    # inside a renderer's body (raw_composited_only) the colour head runs on the samples with density only: the *_live sibling of either call
+    live = _human_role() == 'composite' and human_net.live_route(precision, 'composite', R * S)
+    lws, lbytes = vanilla.live_workspace_for(R * S, 0, dev) if live else (None, 0)
+    tail = (_lib.dev_ptr(lws, torch.uint8), lbytes, 0, _lib.stream_ptr()) if live else (_lib.stream_ptr(),)
     if grid is None:
         ws = _ws(_lib.lib().nm_render_rays_human_workspace_floats(R, S, int(posed)), dev)
-        _lib.check(_lib.lib().nm_render_rays_human(
+        entry = _lib.lib().nm_render_rays_human_live if live else _lib.lib().nm_render_rays_human
+        _lib.check(entry(
             human_net.handle(), mesh.handle if posed else None, _lib.dev_ptr(mesh.T, torch.float64, 'T') if posed else None, _lib.dev_ptr(o.contiguous()),
             _lib.dev_ptr(d.contiguous()), _lib.dev_ptr(near.reshape(-1).contiguous()), _lib.dev_ptr(far.reshape(-1).contiguous()), R, S, _lib.dev_ptr(t_vals), 1,
-            float(sigma_scale), human_net._prec(precision, 'shading'), _lib.dev_ptr(ws), _lib.dev_ptr(raw), _lib.dev_ptr(z), None, None, None, _lib.stream_ptr()),
-            "nm_render_rays_human")
+            float(sigma_scale), human_net._prec(precision, 'shading'), _lib.dev_ptr(ws), _lib.dev_ptr(raw), _lib.dev_ptr(z), None, None, None, *tail),
+            "nm_render_rays_human_live" if live else "nm_render_rays_human")
     else:
         # empty-space skipping (occupancy.py, K11b): the grid is tested on the canonical points -- o + d z (canonical render) or the warped
         # points (posed); skipped samples keep raw = 0.  Same workspace prefix as nm_render_rays_human (the trace below reads it).
         grid.check_device(dev)
         counts = torch.zeros(2, device=dev, dtype=torch.int32)
         ws = _ws(_lib.lib().nm_render_rays_human_occ_workspace_floats(R, S, int(posed)), dev)
-        _lib.check(_lib.lib().nm_render_rays_human_occ(
+        entry = _lib.lib().nm_render_rays_human_occ_live if live else _lib.lib().nm_render_rays_human_occ
+        _lib.check(entry(
             human_net.handle(), mesh.handle if posed else None, _lib.dev_ptr(mesh.T, torch.float64, 'T') if posed else None,
             _lib.dev_ptr(grid.bits, torch.int32), grid.res, grid.box_c(), _lib.dev_ptr(o.contiguous()), _lib.dev_ptr(d.contiguous()),
             _lib.dev_ptr(near.reshape(-1).contiguous()), _lib.dev_ptr(far.reshape(-1).contiguous()), R, S, _lib.dev_ptr(t_vals), 1, float(sigma_scale),
             human_net._prec(precision, 'shading'), _lib.dev_ptr(ws), _lib.dev_ptr(raw), _lib.dev_ptr(z), _lib.dev_ptr(counts, torch.int32), None, None, None,
-            _lib.stream_ptr()), "nm_render_rays_human_occ")
+            *tail), "nm_render_rays_human_occ_live" if live else "nm_render_rays_human_occ")
         if trace is not None:
             _note(trace, occupancy_human={'evaluated': int(counts[0].item()), 'total': R * S})
     if trace is not None:
@@ -500,6 +547,15 @@ def render_smpl_nerf_rays(human_net, o, d, posed_verts, mesh, samples_per_ray, w
     rgb = torch.full((R, 3), 1.0 if white_bkg else 0.0, device=o.device, dtype=torch.float32)    # misses, :199-205
     depth = torch.zeros(R, device=o.device, dtype=torch.float32)
     acc = torch.zeros(R, device=o.device, dtype=torch.float32)
+    with raw_composited_only(min(R, MAX_RAYS_PER_LAUNCH) * int(samples_per_ray), o.device):      # (raw -> raw2outputs, nothing else)
+        _render_smpl_nerf_batches(human_net, o, d, posed_verts, mesh, samples_per_ray, white_bkg, render_can, geo_threshold, interval_comp, precision, trace, given,
+                                  rgb, depth, acc)
+    return rgb, depth, acc
+
+
+def _render_smpl_nerf_batches(human_net, o, d, posed_verts, mesh, samples_per_ray, white_bkg, render_can, geo_threshold, interval_comp, precision, trace, given,
+                              rgb, depth, acc):
+    R = o.shape[0]
     for i, j in _chunks(R):
         oc, dc = o[i:j].contiguous(), d[i:j].contiguous()
         near, far = _given_near_far(given, 0, i, j, oc, dc, posed_verts, geo_threshold)
@@ -520,7 +576,6 @@ def render_smpl_nerf_rays(human_net, o, d, posed_verts, mesh, samples_per_ray, w
         ray_utils.scatter_rows(rgb[i:j], hit, _rgb)
         ray_utils.scatter_rows(depth[i:j], hit, _depth)
         ray_utils.scatter_rows(acc[i:j], hit, _acc)
-    return rgb, depth, acc
 
 
 def render_hybrid_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far, posed_verts, mesh, samples_per_ray,
@@ -532,7 +587,16 @@ def render_hybrid_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far,
     intervals bound the merged transmittance from above; behind the body the background sees its own x the body's): a pixel moves
     by < 2 eps, for bodies of any opacity (tests/test_hip_march.py: opaque and semi-transparent).
     The plain case (no trace, no replay, no termination, no occupancy grid on any of the nets) is ONE C call per batch: render_hybrid_rays_fused,
-    bit-identical."""
+    bit-identical.  Every raw of the body falls under the composite-only rule (LIVE_HEADS above): raw2outputs, merge_composite_lists,
+    transmittance_of and the marches' nm_transmittance_chunk* are all that read it."""
+    S_max = int(samples_per_ray) + (int(importance_samples_per_ray) if fine_bkg is not None else 0)
+    with raw_composited_only(min(o.shape[0], MAX_RAYS_PER_LAUNCH) * S_max, o.device):
+        return _render_hybrid_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far, posed_verts, mesh, samples_per_ray, importance_samples_per_ray,
+                                   white_bkg, geo_threshold, precision, trace, given)
+
+
+def _render_hybrid_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far, posed_verts, mesh, samples_per_ray, importance_samples_per_ray, white_bkg,
+                        geo_threshold, precision, trace, given):
     if TERMINATION_EPS <= 0 and trace is None and given is None and not _occupancy_on(coarse_bkg, fine_bkg) and occupancy.grid_of(human_net) is None:
         return render_hybrid_rays_fused(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far, posed_verts, mesh, samples_per_ray,
                                         importance_samples_per_ray, white_bkg, geo_threshold, precision)
@@ -584,10 +648,11 @@ def render_hybrid_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far,
                 ray_utils.scatter_rows(z_far, hit, hf.reshape(-1))
                 ray_utils.scatter_rows(T_occ, hit, transmittance_of(h_raw, h_z, hd, dz_h))
                 occluder = (z_far, T_occ)
-            bkg_raw = bkg_shade(fine_bkg if fine_bkg is not None else coarse_bkg, oc, dc, bkg_z, precision, trace, occluder, dz_b.contiguous())
+            bkg_raw = bkg_shade(fine_bkg if fine_bkg is not None else coarse_bkg, oc, dc, bkg_z, precision, trace, occluder, dz_b.contiguous(),
+                                composite_only=LIVE_HEADS)
         else:
             bkg_raw, bkg_z = bkg_pass_rays(coarse_bkg, fine_bkg, oc, dc, n, f, samples_per_ray, importance_samples_per_ray,
-                                           white_bkg, precision, trace, given_z)
+                                           white_bkg, precision, trace, given_z, composite_only=LIVE_HEADS)
             hit, hd, hf, h_raw, h_z = human_lists()
         # every ray first gets the background-only composite (what the reference does for misses, :303-311) ...
         rgb[i:j], _, _, _, depth[i:j] = raw2outputs(bkg_raw, bkg_z, dc, white_bkg=white_bkg, want_weights=False)
@@ -603,9 +668,10 @@ def render_hybrid_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far,
 
 
 def render_hybrid_rays_fused(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far, posed_verts, mesh, samples_per_ray,
-                             importance_samples_per_ray, white_bkg=True, geo_threshold=DEFAULT_GEO_THRESH, precision=None):
+                             importance_samples_per_ray, white_bkg=True, geo_threshold=DEFAULT_GEO_THRESH, precision=None, live=None):
     """render_hybrid_rays' batch body as ONE C call (nm_render_rays_hybrid): same kernels, same bits; no trace / replay / early
-    termination hooks -- the plain path of a frame render."""
+    termination hooks -- the plain path of a frame render.  live (default: LIVE_HEADS): nm_render_rays_hybrid_live -- the fine background pass
+    and the hit rays' human pass evaluate the colour head on their live samples only; rgb, depth and acc are bit-identical."""
     _lib.require_gpu()
     R = o.shape[0]
     dev = o.device
@@ -620,18 +686,24 @@ def render_hybrid_rays_fused(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bk
     # synchronisation): ~28 KB per ray at 128 + 128 + 128 samples, so batches of FUSED_HYBRID_RAYS rays (3.7 GB) and ONE workspace
     step = min(MAX_RAYS_PER_LAUNCH, FUSED_HYBRID_RAYS)
     ws = _ws(_lib.lib().nm_render_rays_hybrid_workspace_floats(min(R, step), S, N, Sh), dev)
+    precs = (coarse_bkg._prec(precision, None if fine_bkg is not None else 'shading'), fine_bkg._prec(precision, 'shading') if fine_bkg is not None else 0,
+             human_net._prec(precision, 'shading'))
+    n_live = min(R, step) * max(S + N, Sh)                                           # the larger of the two composited passes of a batch
+    live = (LIVE_HEADS if live is None else bool(live)) and n_live >= vanilla.LIVE_MIN_SAMPLES and _lib.NM_PREC_I8X3 in (precs[1] if N else precs[0], precs[2])
+    lws, lbytes = vanilla.live_workspace_for(n_live, 0, dev) if live else (None, 0)
+    tail = (_lib.dev_ptr(lws, torch.uint8), lbytes, 0, _lib.stream_ptr()) if live else (_lib.stream_ptr(),)
+    entry = _lib.lib().nm_render_rays_hybrid_live if live else _lib.lib().nm_render_rays_hybrid
     for i in range(0, R, step):
         j = min(i + step, R)
         oc, dc = o[i:j].contiguous(), d[i:j].contiguous()
         n = j - i
         r_, d_, a_ = rgb[i:j], depth[i:j], acc[i:j]
-        _lib.check(_lib.lib().nm_render_rays_hybrid(
+        _lib.check(entry(
             coarse_bkg.handle(), fine_bkg.handle() if fine_bkg is not None else None, human_net.handle(), mesh.handle, _lib.dev_ptr(mesh.T, torch.float64, 'T'),
             _lib.dev_ptr(verts), verts.shape[0], float(geo_threshold), _lib.dev_ptr(oc), _lib.dev_ptr(dc), n, float(bkg_near), float(bkg_far), S, N, Sh,
             _lib.dev_ptr(t_vals), _lib.dev_ptr(u), _lib.dev_ptr(t_vals), int(bool(white_bkg)),
-            coarse_bkg._prec(precision, None if fine_bkg is not None else 'shading'), fine_bkg._prec(precision, 'shading') if fine_bkg is not None else 0,
-            human_net._prec(precision, 'shading'), _lib.dev_ptr(ws), _lib.dev_ptr(r_), _lib.dev_ptr(d_), _lib.dev_ptr(a_), _lib.stream_ptr()),
-            "nm_render_rays_hybrid")
+            precs[0], precs[1], precs[2], _lib.dev_ptr(ws), _lib.dev_ptr(r_), _lib.dev_ptr(d_), _lib.dev_ptr(a_), *tail),
+            "nm_render_rays_hybrid_live" if live else "nm_render_rays_hybrid")
     return rgb, depth, acc
 
 
@@ -641,7 +713,17 @@ def render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far,
     """Device core of render_hybrid_nerf_multi_persons -> (rgb [R,3], depth [R]) CUDA  (render_utils.py:390-456).  `given`: see
     bkg_pass_rays.  TERMINATION_EPS > 0: as render_hybrid_rays (sample positions of all lists, then the actors, then the background
     shading pass, each marched on the transmittance of its samples over their intervals in the MERGED list; the background behind the
-    farthest body a ray hits on its own x all the bodies'); a pixel moves by < (1 + actors) eps."""
+    farthest body a ray hits on its own x all the bodies'); a pixel moves by < (1 + actors) eps.  The composite-only rule (LIVE_HEADS above) holds
+    for every raw of the body but one: with TERMINATION_EPS > 0 the marched background pass tells "never reached" from the colours of its last
+    sample, so that pass stays whole-network ('shading')."""
+    S_max = int(samples_per_ray) + (int(importance_samples_per_ray) if fine_bkg is not None else 0)
+    with raw_composited_only(min(o.shape[0], MAX_RAYS_PER_LAUNCH) * S_max, o.device):
+        return _render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far, posed_verts, meshes, samples_per_ray, importance_samples_per_ray,
+                                  white_bkg, geo_threshold, precision, trace, given)
+
+
+def _render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far, posed_verts, meshes, samples_per_ray, importance_samples_per_ray, white_bkg,
+                       geo_threshold, precision, trace, given):
     R = o.shape[0]
     rgb = torch.empty((R, 3), device=o.device, dtype=torch.float32)
     depth = torch.empty(R, device=o.device, dtype=torch.float32)
@@ -733,7 +815,7 @@ def render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far,
             raw_all = bkg_shade(fine_bkg if fine_bkg is not None else coarse_bkg, oc, dc, z_all, precision, trace, (z_far, T_occ), dz_l[0])
         else:
             raw_all, z_all = bkg_pass_rays(coarse_bkg, fine_bkg, oc, dc, n, f, samples_per_ray, importance_samples_per_ray,
-                                           white_bkg, precision, trace, given_z)
+                                           white_bkg, precision, trace, given_z, composite_only=LIVE_HEADS)
         # In this renderer the terminal 1e10 interval sits on an actor's zero-density placeholder whenever a ray misses one
         # (render_utils.py:418-419), so the LAST background sample is followed by a finite interval of ~far..2 far instead:
         # alpha = 1 - exp(-sigma * 3.14..) is then ~300x as sensitive to that one sigma as a sample inside the ray is.  Under the

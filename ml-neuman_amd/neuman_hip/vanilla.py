@@ -6,6 +6,7 @@ NeRF :95-152, Joiner :155-166, build_nerf :208-250), so reference checkpoints lo
 pointers to ``nm_mlp_forward`` (fused PE + MLP kernel, csrc/mlp.hip).  There is no torch/CPU evaluation
 of the network in this package; calling it with CPU tensors or with autograd enabled raises.
 """
+import contextlib
 import ctypes
 import os
 
@@ -123,6 +124,41 @@ def with_absent_columns(tensors, pads):
     return out
 
 
+# The smallest pass that takes the trunk / colour-head pair in forward, forward_ray_chunk and the occupancy forms.  The pair replaces one launch
+# with a counter reset plus two, so a small pass loses: measured (tools/live_heads_time.py --sweep; profiles/live_heads_all_passes.md, "Small
+# passes") the pair is 11-36 us slower up to 2^18 samples and 14 us faster at 2^19, the smallest size at which it is not slower.
+LIVE_MIN_SAMPLES = 1 << 19
+
+_live_ws = None                                  # the workspace a renderer call shares among its passes (live_workspace)
+
+
+@contextlib.contextmanager
+def live_workspace(n_max, device, chunk_samples=0):
+    """One nm_mlp_*_live workspace for every pass inside the block (they run one after another on the current stream), sized for a pass
+    of n_max samples: allocated on first use, released at the end.  A pass that needs more allocates its own."""
+    global _live_ws
+    outer = _live_ws
+    _live_ws = [int(n_max), int(chunk_samples), torch.device(device), None]
+    try:
+        yield
+    finally:
+        _live_ws = outer
+
+
+def live_workspace_for(n, chunk_samples, device, nbytes=None):
+    """-> (uint8 workspace, bytes the entry is told) for a live pass of n samples: the open live_workspace where it is large enough, else a
+    buffer of the pass's own.  nbytes: what the entry needs when that is not nm_mlp_live_workspace_bytes(n, chunk_samples)"""
+    if nbytes is None:
+        nbytes = int(_lib.lib().nm_mlp_live_workspace_bytes(int(n), int(chunk_samples)))
+    w = _live_ws
+    if w is not None and w[2] == torch.device(device):
+        if w[3] is None:
+            w[3] = torch.empty((int(_lib.lib().nm_mlp_live_workspace_bytes(max(w[0], int(n)), w[1])),), device=device, dtype=torch.uint8)
+        if w[3].numel() >= nbytes:
+            return w[3], nbytes
+    return torch.empty((nbytes,), device=device, dtype=torch.uint8), nbytes
+
+
 class Joiner(nn.Module):
     """PE + MLP, evaluated by the fused HIP kernel (reference vanilla.py:155-166)."""
 
@@ -217,6 +253,13 @@ class Joiner(nn.Module):
             p = 'i8x3' if role in ('shading', 'composite') else 'fp16x3'
         return _lib.PRECISIONS[p]
 
+    def live_route(self, precision, role, n, sigma_only=False):
+        """Does a pass of n samples tagged `role` run as the trunk / colour-head pair (forward, forward_ray_chunk, occupancy.forward_rays,
+        occupancy.forward_points)?  role='composite' on the view-dependent net in i8x3, from LIVE_MIN_SAMPLES samples up; everywhere else
+        'composite' is the i8x3 whole-network launch that 'shading' is."""
+        return (role == 'composite' and not sigma_only and self.nerf.use_viewdirs and n >= LIVE_MIN_SAMPLES
+                and self._prec(precision, role) == _lib.NM_PREC_I8X3)
+
     @staticmethod
     def _guard(*tensors):
         _lib.require_gpu()
@@ -224,9 +267,10 @@ class Joiner(nn.Module):
             raise _lib.NeumanHipError("the rendering kernels are forward-only: wrap in torch.no_grad(), or put the Joiner in train() mode "
                                        "for the differentiable float32 forward (neuman_hip/train.py)")
 
-    def forward(self, input_pts, input_views=None, precision=None, sigma_scale=1.0, role=None):
+    def forward(self, input_pts, input_views=None, precision=None, sigma_scale=1.0, role=None, chunk_samples=0):
         """input_pts [..., 3], input_views [..., 3] (CUDA f32) -> [..., 4] = (r, g, b, sigma).  The plain-head net
-        (use_viewdirs=False) ignores the views like the reference (vanilla.py:122-123) and accepts None."""
+        (use_viewdirs=False) ignores the views like the reference (vanilla.py:122-123) and accepts None.
+        role='composite': as forward_rays (nm_mlp_forward_live; live_route says when)."""
         if input_views is None:
             if self.nerf.use_viewdirs:
                 raise _lib.NeumanHipError("input_views is required by the use_viewdirs=True net (vanilla.py:133-134)")
@@ -252,6 +296,12 @@ class Joiner(nn.Module):
         p = input_pts.detach().reshape(-1, 3).contiguous()
         d = input_views.detach().reshape(-1, 3).contiguous()
         out = torch.empty((p.shape[0], 4), device=p.device, dtype=torch.float32)
+        if self.live_route(precision, role, p.shape[0]):
+            ws, nbytes = live_workspace_for(p.shape[0], chunk_samples, p.device)
+            _lib.check(_lib.lib().nm_mlp_forward_live(self.handle(), _lib.dev_ptr(p, name='input_pts'), _lib.dev_ptr(d, name='input_views'), p.shape[0],
+                                                      self._prec(precision, role), float(sigma_scale), _lib.dev_ptr(out), _lib.dev_ptr(ws, torch.uint8), nbytes,
+                                                      int(chunk_samples), _lib.stream_ptr()), "nm_mlp_forward_live")
+            return out.reshape(*shp, 4)
         _lib.check(_lib.lib().nm_mlp_forward(self.handle(), _lib.dev_ptr(p, name='input_pts'), _lib.dev_ptr(d, name='input_views'),
                                              p.shape[0], self._prec(precision, role), float(sigma_scale), _lib.dev_ptr(out),
                                              _lib.stream_ptr()), "nm_mlp_forward")
@@ -277,8 +327,8 @@ class Joiner(nn.Module):
         R, S = z_vals.shape
         out = torch.empty((R, S, 4), device=z_vals.device, dtype=torch.float32)
         if role == 'composite' and not sigma_only and self.nerf.use_viewdirs and self._prec(precision, role) == _lib.NM_PREC_I8X3:
-            nbytes = _lib.lib().nm_mlp_forward_rays_live_workspace_bytes(R, S, int(chunk_samples))
-            ws = torch.empty((nbytes,), device=z_vals.device, dtype=torch.uint8)
+            nbytes = int(_lib.lib().nm_mlp_forward_rays_live_workspace_bytes(R, S, int(chunk_samples)))
+            ws, _ = live_workspace_for(R * S, chunk_samples, z_vals.device, nbytes)  # (a renderer call's one workspace where it is large enough)
             _lib.check(_lib.lib().nm_mlp_forward_rays_live(
                 self.handle(), _lib.dev_ptr(origin, name='origin'), _lib.dev_ptr(direction, name='direction'), _lib.dev_ptr(z_vals, name='z_vals'), R, S,
                 self._prec(precision, role), float(sigma_scale), _lib.dev_ptr(out), _lib.dev_ptr(ws, torch.uint8), nbytes, int(chunk_samples),
@@ -291,12 +341,23 @@ class Joiner(nn.Module):
         return out
 
     def forward_ray_chunk(self, origin, direction, z_vals, ray_idx, n_rays_dev, s0, chunk, out, precision=None, sigma_scale=1.0, role=None,
-                          sigma_only=False):
+                          sigma_only=False, chunk_samples=0):
         """One chunk of a front-to-back march (nm_mlp_forward_ray_chunk): samples s0 .. s0+chunk-1 of the rays listed in
         `ray_idx` (int32; only its first *n_rays_dev entries are live -- the count stays on the device) are evaluated and written
-        into `out` [R,S,4]; nothing else of `out` is touched.  sigma_only: as forward_rays."""
+        into `out` [R,S,4]; nothing else of `out` is touched.  sigma_only: as forward_rays.  role='composite': as forward_rays
+        (nm_mlp_forward_ray_chunk_live; live_route says when)."""
         self._guard(origin, direction, z_vals)
         R, S = z_vals.shape
+        n = ray_idx.shape[0] * int(chunk)
+        # (the list carries a record of `out` as int32: nm_mlp_forward_ray_chunk_live cannot check that itself, R is not among its arguments)
+        if self.live_route(precision, role, n, sigma_only) and R * S < (1 << 31):
+            ws, nbytes = live_workspace_for(n, chunk_samples, z_vals.device)
+            _lib.check(_lib.lib().nm_mlp_forward_ray_chunk_live(
+                self.handle(), _lib.dev_ptr(origin, name='origin'), _lib.dev_ptr(direction, name='direction'), _lib.dev_ptr(z_vals, name='z_vals'), S,
+                _lib.dev_ptr(ray_idx, torch.int32, 'ray_idx'), _lib.dev_ptr(n_rays_dev, torch.int32, 'n_rays_dev'), ray_idx.shape[0], int(s0), int(chunk),
+                self._prec(precision, role), float(sigma_scale), _lib.dev_ptr(out), _lib.dev_ptr(ws, torch.uint8), nbytes, int(chunk_samples),
+                _lib.stream_ptr()), "nm_mlp_forward_ray_chunk_live")
+            return out
         entry = _lib.lib().nm_mlp_sigma_ray_chunk if sigma_only else _lib.lib().nm_mlp_forward_ray_chunk
         _lib.check(entry(
             self.handle(), _lib.dev_ptr(origin, name='origin'), _lib.dev_ptr(direction, name='direction'), _lib.dev_ptr(z_vals, name='z_vals'), S,

@@ -1,6 +1,10 @@
 """The bench frame's fine pass (640 000 rays x 256 samples on the bench's own sample positions): the whole-network launch (role='shading') against the
 trunk / head pair (role='composite', nm_mlp_forward_rays_live) at several chunk sizes -- HIP events, best and all of 3 -- and the live fraction the
-device finds.  profiles/live_heads.md records a run."""
+device finds.  profiles/live_heads.md records a run.
+
+--sweep: the small passes instead -- n points of the same scene (the fine net's own live fraction) through Joiner.forward, whole-network launch
+against the pair (a counter reset plus two launches) inside one shared live workspace as the renderers run it, 20 launches each after 3 to warm
+up, for n = 2^8 .. 2^20: the smallest n at which the pair is not slower is vanilla.LIVE_MIN_SAMPLES.  profiles/live_heads_all_passes.md records a run."""
 import os
 import sys
 
@@ -8,11 +12,51 @@ ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
 sys.path.insert(0, os.path.join(ROOT, "ml-neuman_amd"))
 import torch  # noqa: E402
 
-from neuman_hip import ray_utils, render_utils, synthetic  # noqa: E402
+from neuman_hip import ray_utils, render_utils, synthetic, vanilla  # noqa: E402
 
 dev = torch.device('cuda')
 coarse, fine = synthetic.make_joiner(0).to(dev), synthetic.make_joiner(1).to(dev)
 coarse.precision = fine.precision = 'mixed'
+
+
+def sweep():
+    vanilla.LIVE_MIN_SAMPLES = 0
+    g = torch.Generator(device=dev).manual_seed(0)
+    n_max = 1 << 20
+    cap = synthetic.SimpleCapture(800, 800)
+    o, d = ray_utils.shot_all_rays_dev(cap, dev)
+    pick = torch.randint(0, o.shape[0], (n_max,), device=dev, generator=g)
+    zz = float(cap.near['bkg']) + torch.rand((n_max, 1), device=dev, generator=g) * (float(cap.far['bkg']) - float(cap.near['bkg']))
+    pts, dirs = (o[pick] + d[pick] * zz).contiguous(), d[pick].contiguous()
+
+    def timed(n, role, reps=20):
+        p, v = pts[:n].contiguous(), dirs[:n].contiguous()
+        for _ in range(3):
+            out = fine(p, v, role=role)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            out = fine(p, v, role=role)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3, out
+
+    with torch.no_grad(), vanilla.live_workspace(n_max, dev):
+        for k in range(8, 21):
+            n = 1 << k
+            w1, ref = timed(n, 'shading')
+            l1, got = timed(n, 'composite')
+            w2, _ = timed(n, 'shading')
+            l2, _ = timed(n, 'composite')
+            alive = ref[..., 3] > 0
+            same = torch.equal(got[..., 3], ref[..., 3]) and torch.equal(got[..., :3][alive], ref[..., :3][alive])
+            print(f"n 2^{k:<2d} = {n:8d}  live {alive.float().mean().item():.3f}  whole {w1:9.1f} {w2:9.1f} us  pair {l1:9.1f} {l2:9.1f} us  "
+                  f"pair - whole {min(l1, l2) - min(w1, w2):+9.1f} us  live records equal: {same}", flush=True)
+
+
+if '--sweep' in sys.argv:
+    sweep()
+    sys.exit(0)
 cap = synthetic.SimpleCapture(800, 800)
 o, d = ray_utils.shot_all_rays_dev(cap, dev)
 R = o.shape[0]
