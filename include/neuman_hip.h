@@ -444,7 +444,7 @@ int nm_bary_backward(const float* verts, const int32_t* tri, const float* closes
  *   nm_smpl_create copies the model to the device.  HOST pointers, float32 as the reference registers them
  *   (smpl.py:74-107): v_template [V,3], shapedirs [V,3,NB], j_regressor [J,V], parents [J] (parents[0]
  *   ignored, parents[j] < j), lbs_weights [V,J], da_pose [J*3] (the canonical pose: neuman_helper.py:294-299).
- *   J <= 64, NB <= 32.
+ *   J <= 64, 1 <= NB <= 32 (a model without shape directions is refused: every entry takes a betas array).
  *   nm_smpl_frames, per frame b of B (DEVICE pointers): poses [B,J*3] f32, betas [B,NB] f32,
  *   alignments [B,4,4] f64 = the matrix whose TRANSPOSE the reference applies (read_smpls' temp_alignment,
  *   vertex_forward's alignments[idx]).  Rows 0..V-1 are vertices, rows V..V+J-1 the joints

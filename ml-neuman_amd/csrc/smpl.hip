@@ -660,7 +660,8 @@ int nm_smpl_destroy(nm_smpl_t m) {
 int nm_smpl_create(const float* v_template, const float* shapedirs, const float* j_regressor, const int32_t* parents, const float* lbs_weights,
                    const float* da_pose, int V, int J, int NB, nm_smpl_t* out) {
     NM_REQUIRE(v_template && shapedirs && j_regressor && parents && lbs_weights && da_pose && out, "nm_smpl_create: null pointer");
-    NM_REQUIRE(V >= 1 && J >= 1 && J <= kMaxJoints && NB >= 0 && NB <= kMaxBetas, "nm_smpl_create: bad sizes V=%d J=%d NB=%d (J <= %d, NB <= %d)", V,
+    // (NB = 0 would leave every entry with an empty betas array, whose device pointer is null: refused here, by name, rather than there as a "null pointer")
+    NM_REQUIRE(V >= 1 && J >= 1 && J <= kMaxJoints && NB >= 1 && NB <= kMaxBetas, "nm_smpl_create: bad sizes V=%d J=%d NB=%d (J <= %d, 1 <= NB <= %d)", V,
                J, NB, kMaxJoints, kMaxBetas);
     for (int j = 1; j < J; ++j)
         NM_REQUIRE(parents[j] >= 0 && parents[j] < j, "nm_smpl_create: parents[%d] = %d is not an earlier joint", j, parents[j]);
