@@ -244,11 +244,24 @@ int nm_mlp_forward_rays(nm_mlp_t mlp, const float* origin, const float* directio
  * net and NEUMAN_I8_KERNEL=w run nm_mlp_forward_rays itself.  The rays are walked in chunks of chunk_samples samples (whole rays; <= 0:
  * NM_LIVE_CHUNK_SAMPLES); per chunk a counter reset, a trunk launch that lists the live samples with their activations (520 B each) in
  * `workspace`, and a head launch sized on the device from that list -- no host synchronisation.  workspace (16-byte aligned):
- * nm_mlp_forward_rays_live_workspace_bytes(R, S, chunk_samples) bytes = one chunk with every sample live. */
+ * nm_mlp_forward_rays_live_workspace_bytes(R, S, chunk_samples) bytes = one chunk with every sample live.  Where that workspace is large enough the
+ * whole call is ONE launch instead (nm_mlp_forward_rays_fused below: same records, no chunks). */
 #define NM_LIVE_CHUNK_SAMPLES (1 << 21)
 int64_t nm_mlp_forward_rays_live_workspace_bytes(int64_t R, int S, int64_t chunk_samples);
 int nm_mlp_forward_rays_live(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S, int precision,
                              float sigma_scale, float* out, void* workspace, int64_t workspace_bytes, int64_t chunk_samples, nm_stream_t stream);
+/* The pair as ONE persistent launch (csrc/mlp_i8f.hip): every workgroup lists the live samples of its own trunk tiles in a ring of 768 entries of its
+ * own and runs colour-head tiles on them between its trunk tiles -- no chunks, no global counter, no reset; every record bit-identical to the pair's.
+ * nm_mlp_forward_rays_live takes it for a call with R * S < 2^31 whose workspace (sized as above) also holds
+ * nm_mlp_live_fused_workspace_bytes(R * S) bytes = min(ceil(n / 256), 256) lists of 768 * 520 B and two int32 per list (rounded up to 256 B), which is
+ * every call of frame size; NEUMAN_LIVE_FUSED=0 keeps the pair for every call, =1 takes the fused launch, unset: NM_LIVE_FUSED_DEFAULT.
+ * nm_mlp_forward_rays_fused runs the fused launch itself, on a workspace of at least that size, whatever the switch says (an error for the plain-head
+ * net and under NEUMAN_I8_KERNEL=w: there is no such kernel).  After the call the workspace's last block holds, per workgroup, the trunk tiles and the
+ * head tiles it ran (int32 [groups][2] at byte groups * 768 * 520, groups = min(ceil(n / 256), 256); the launch takes min(groups, CUs) workgroups). */
+#define NM_LIVE_FUSED_DEFAULT 1
+int64_t nm_mlp_live_fused_workspace_bytes(int64_t n);
+int nm_mlp_forward_rays_fused(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S, float sigma_scale,
+                              float* out, void* workspace, int64_t workspace_bytes, nm_stream_t stream);
 /* Density only, for a pass whose colours the caller discards -- the coarse pass of a two-pass render: the reference
  * composites it (render_utils.py:139) and keeps nothing but the weights that place the importance samples (:141), which
  * depend on sigma alone.  Same arguments as nm_mlp_forward_rays; out [R,S,4] receives (0, 0, 0, sigma * sigma_scale) with

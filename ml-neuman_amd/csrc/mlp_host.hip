@@ -1087,6 +1087,39 @@ static int64_t live_cap(int64_t R, int S, int64_t chunk_samples) {              
     return (live_chunk_rays(R, S, chunk_samples) * S + 255) / 256 * 256;
 }
 
+// NEUMAN_LIVE_FUSED: 1 = the ray form runs the pair as one persistent launch (mlp_i8f.hip) where its workspace allows, 0 = always the pair
+static bool live_fused() {
+    const char* e = getenv("NEUMAN_LIVE_FUSED");                                         // (read per call: the tests switch it inside one process)
+    return e ? !strcmp(e, "1") : NM_LIVE_FUSED_DEFAULT != 0;
+}
+static void live_launch(nm_mlp_t m, nm::MlpLaunch& L) {
+    L.wpack = nullptr; L.bias = nullptr; L.wpack16 = nullptr; L.bias16 = nullptr; L.wstream8 = nullptr;
+    L.petab = m->d_petab;
+    L.pe_kind = m->desc.pe_kind; L.pos_nfreq = m->desc.pos_n_freqs; L.dir_nfreq = m->desc.dir_n_freqs;
+    L.pos_octaves = m->pos_octaves; L.dir_octaves = m->dir_octaves;
+    L.plain_head = 0;
+    L.consts8 = m->d_consts8;
+}
+
+int64_t nm_mlp_live_fused_workspace_bytes(int64_t n) { return n < 0 ? -1 : nm::fused_workspace_bytes(n); }
+
+int nm_mlp_forward_rays_fused(nm_mlp_t m, const float* origin, const float* direction, const float* z_vals, int64_t R, int S, float sigma_scale, float* out,
+                              void* workspace, int64_t workspace_bytes, nm_stream_t stream) {
+    // (checked before the handle is looked at, so that a bad call fails the same way with or without a device)
+    NM_REQUIRE(((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0, "nm_mlp_forward_rays_fused: out and workspace must be 16-byte aligned");
+    NM_REQUIRE(R >= 0 && S >= 1 && R < (1ll << 31) && R * (int64_t)S < (1ll << 31), "nm_mlp_forward_rays_fused: bad sizes (R=%lld S=%d)", (long long)R, S);
+    const int64_t need = nm::fused_workspace_bytes(R * (int64_t)S);
+    NM_REQUIRE((workspace || R == 0) && workspace_bytes >= need, "nm_mlp_forward_rays_fused: workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)need);
+    NM_REQUIRE(R == 0 || (origin && direction && z_vals && out), "nm_mlp_forward_rays_fused: null pointer");
+    NM_REQUIRE(m, "nm_mlp_forward_rays_fused: null handle");
+    NM_REQUIRE(!m->desc.plain_head && i8_as_kernel(), "nm_mlp_forward_rays_fused: no such kernel for the plain-head net or under NEUMAN_I8_KERNEL=w");
+    if (R == 0) return NM_OK;
+    nm::MlpLaunch L;
+    live_launch(m, L);
+    return nm::launch_mlp_i8f(L, m->d_trunk8, (int)nm::kTrunkStreamBytes8, origin, direction, z_vals, R * (int64_t)S, S, sigma_scale, out, workspace,
+                              nm::as_stream(stream));
+}
+
 int64_t nm_mlp_forward_rays_live_workspace_bytes(int64_t R, int S, int64_t chunk_samples) {
     if (R < 0 || S < 1) return -1;
     return live_cap(R, S, chunk_samples) * (512 + 4 + 4) + 256;
@@ -1106,12 +1139,11 @@ int nm_mlp_forward_rays_live(nm_mlp_t m, const float* origin, const float* direc
     const int64_t cap = live_cap(R, S, chunk_samples), rays = live_chunk_rays(R, S, chunk_samples);
     NM_REQUIRE(rays * S < (1ll << 31), "nm_mlp_forward_rays_live: a chunk of %lld samples", (long long)(rays * S));
     nm::MlpLaunch L;
-    L.wpack = nullptr; L.bias = nullptr; L.wpack16 = nullptr; L.bias16 = nullptr; L.wstream8 = nullptr;
-    L.petab = m->d_petab;
-    L.pe_kind = m->desc.pe_kind; L.pos_nfreq = m->desc.pos_n_freqs; L.dir_nfreq = m->desc.dir_n_freqs;
-    L.pos_octaves = m->pos_octaves; L.dir_octaves = m->dir_octaves;
-    L.plain_head = 0;
-    L.consts8 = m->d_consts8;
+    live_launch(m, L);
+    // one persistent launch (mlp_i8f.hip) where the workspace the caller sized for the pair holds its lists too: every call of frame size
+    if (live_fused() && R * (int64_t)S < (1ll << 31) && workspace_bytes >= nm::fused_workspace_bytes(R * (int64_t)S))
+        return nm::launch_mlp_i8f(L, m->d_trunk8, (int)nm::kTrunkStreamBytes8, origin, direction, z_vals, R * (int64_t)S, S, sigma_scale, out, workspace,
+                                  nm::as_stream(stream));
     uint8_t* ws = static_cast<uint8_t*>(workspace);
     nm::LiveList live;
     live.x = reinterpret_cast<uint4*>(ws);

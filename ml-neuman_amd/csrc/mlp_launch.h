@@ -58,6 +58,19 @@ int launch_mlp_i8s(const MlpLaunch& L, const void* image8, const float* pts, con
 // or 4): record k takes dirs[k].  max_entries bounds the grid (the length itself is read on the device)
 int launch_mlp_i8h(const MlpLaunch& L, const void* head8, int in_mode, const float* dirs, const float* direction, int S_total, const LiveList& live,
                    int64_t max_entries, float* out, hipStream_t stream);
+// ... and the pair as one persistent launch over a ray form (mlp_i8f.hip): every workgroup lists its live samples in a ring of kFusedEntries entries of
+// its own (the pair's layout with cap = kFusedEntries: x, then sx, then idx) and shades them behind its own trunk tiles.  workspace:
+// fused_workspace_bytes(n) = one list per workgroup of the widest grid the launch may take (one per 256-sample tile, kFusedMaxGroups at most), then two
+// int32 per workgroup: the trunk and the head tiles it ran.  trunk8 = the trunk cut, head_off = where the head cut stands behind it.  n < 2^31
+constexpr int kFusedEntries = 768, kFusedMaxGroups = 256;
+constexpr int64_t kFusedListBytes = (int64_t)kFusedEntries * (512 + 4 + 4);
+inline int64_t fused_groups(int64_t n) {
+    const int64_t tiles = (n + 255) / 256;
+    return tiles < kFusedMaxGroups ? tiles : kFusedMaxGroups;
+}
+inline int64_t fused_workspace_bytes(int64_t n) { return fused_groups(n) * kFusedListBytes + (fused_groups(n) * 8 + 255) / 256 * 256; }
+int launch_mlp_i8f(const MlpLaunch& L, const void* trunk8, int head_off, const float* origin, const float* direction, const float* z, int64_t n, int S,
+                   float sigma_scale, float* out, void* workspace, hipStream_t stream);
 // NM_PREC_FP16X3 density only, activation-stationary (mlp_f16t.hip); stream16t = sigma_stream_kernel's re-cut of the fp16 image.  dbg (nullable): the
 // activations after stage dbg_stage of the first tile (+ 100 x round) of workgroup 0 as float32 [128 samples][256] in k-slot order
 int sigma_f16t_ndir();       // the NDIR tools/gen_f16t.py emitted mlp_f16t_body.h for: the stream is cut for exactly that

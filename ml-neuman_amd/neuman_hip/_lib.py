@@ -83,6 +83,8 @@ SIGNATURES = {
     "nm_mlp_forward_rays_live_workspace_bytes": (i64, [i64, i32, i64]),
     "nm_mlp_forward_rays_live": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, i32, ctypes.c_float, c_f32p, ctypes.c_void_p, i64, i64, c_stream]),
     "nm_mlp_sigma_rays": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, i32, ctypes.c_float, c_f32p, c_stream]),
+    "nm_mlp_live_fused_workspace_bytes": (i64, [i64]),
+    "nm_mlp_forward_rays_fused": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, ctypes.c_float, c_f32p, ctypes.c_void_p, i64, c_stream]),
     "nm_mlp_live_workspace_bytes": (i64, [i64, i64]),
     "nm_mlp_forward_live": (i32, [ctypes.c_void_p, c_f32p, c_f32p, i64, i32, ctypes.c_float, c_f32p, ctypes.c_void_p, i64, i64, c_stream]),
     "nm_mlp_forward_listed_live": (i32, [ctypes.c_void_p, c_f32p, c_f32p, i64, c_i32p, c_i32p, i64, i32, ctypes.c_float, c_f32p, ctypes.c_void_p, i64, i64,

@@ -321,13 +321,15 @@ class Joiner(nn.Module):
         sigma_only: the caller uses nothing but out[..., 3] (a coarse pass that only places importance samples) -- the
         colour head is skipped where the kernel can (out[..., :3] = 0), sigma is bit-identical either way.
         role='composite': the caller composites the result and does nothing else with it -- samples whose density is <= 0 (weight
-        exactly 0) come back with colour 0 and the colour head runs on the others only (nm_mlp_forward_rays_live, in chunks of
-        `chunk_samples`; 0: the library's default); every other record is bit-identical to role='shading'."""
+        exactly 0) come back with colour 0 and the colour head runs on the others only (nm_mlp_forward_rays_live: one persistent launch, or under NEUMAN_LIVE_FUSED=0
+        a trunk and a head launch per chunk of `chunk_samples`; 0: the library's default); every other record is bit-identical to role='shading'."""
         self._guard(origin, direction, z_vals)
         R, S = z_vals.shape
         out = torch.empty((R, S, 4), device=z_vals.device, dtype=torch.float32)
         if role == 'composite' and not sigma_only and self.nerf.use_viewdirs and self._prec(precision, role) == _lib.NM_PREC_I8X3:
             nbytes = int(_lib.lib().nm_mlp_forward_rays_live_workspace_bytes(R, S, int(chunk_samples)))
+            if R * S < (1 << 31):                                # room for the one-launch form too (NEUMAN_LIVE_FUSED; at most 102 MB, a frame's pair needs more)
+                nbytes = max(nbytes, int(_lib.lib().nm_mlp_live_fused_workspace_bytes(R * S)))
             ws, _ = live_workspace_for(R * S, chunk_samples, z_vals.device, nbytes)  # (a renderer call's one workspace where it is large enough)
             _lib.check(_lib.lib().nm_mlp_forward_rays_live(
                 self.handle(), _lib.dev_ptr(origin, name='origin'), _lib.dev_ptr(direction, name='direction'), _lib.dev_ptr(z_vals, name='z_vals'), R, S,

@@ -1,6 +1,7 @@
 """The bench frame's fine pass (640 000 rays x 256 samples on the bench's own sample positions): the whole-network launch (role='shading') against the
-trunk / head pair (role='composite', nm_mlp_forward_rays_live) at several chunk sizes -- HIP events, best and all of 3 -- and the live fraction the
-device finds.  profiles/live_heads.md records a run.
+trunk / head pair (role='composite', nm_mlp_forward_rays_live) at several chunk sizes and against the pair as one persistent launch
+(NEUMAN_LIVE_FUSED=1, csrc/mlp_i8f.hip) -- HIP events, best and all of 3 -- and the live fraction the device finds.  profiles/live_heads.md and
+profiles/live_fused.md record runs.
 
 --sweep: the small passes instead -- n points of the same scene (the fine net's own live fraction) through Joiner.forward, whole-network launch
 against the pair (a counter reset plus two launches) inside one shared live workspace as the renderers run it, 20 launches each after 3 to warm
@@ -68,7 +69,10 @@ with torch.no_grad():
     torch.cuda.synchronize()
     live = int((ref[..., 3] > 0).sum())
     print(f"rays {R}, samples {z.numel()}, live {live} = {live / z.numel():.4f}", flush=True)
-    for tag, kw in [('whole', dict(role='shading'))] + [(f'live 2^{k}', dict(role='composite', chunk_samples=1 << k)) for k in (20, 21, 22, 23, 24)] + [('whole', dict(role='shading')), ('live 2^22', dict(role='composite', chunk_samples=1 << 22))]:
+    arms = ([('whole', dict(role='shading')), ('fused', dict(role='composite'))] + [(f'live 2^{k}', dict(role='composite', chunk_samples=1 << k)) for k in (20, 21, 22, 23, 24)]
+            + [('whole', dict(role='shading')), ('fused', dict(role='composite')), ('live 2^21', dict(role='composite', chunk_samples=1 << 21))])
+    for tag, kw in arms:
+        os.environ['NEUMAN_LIVE_FUSED'] = '1' if tag == 'fused' else '0'           # (read per call: the one persistent launch | the pair in chunks)
         ms = []
         for _ in range(3):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
