@@ -564,6 +564,40 @@ int nm_render_rays_hybrid_live(nm_mlp_t coarse, nm_mlp_t fine, nm_mlp_t human, n
  * z / raw / rows / S are HOST arrays of k entries. */
 int nm_merge_composite_lists(int k, const float* const* z, const float* const* raw, const int32_t* const* rows, const int* S, int64_t R,
                              const float* rays_d, int white_bkg, float* rgb, float* depth, float* acc, nm_stream_t stream);
+/* nm_merge_composite_lists for 1 <= k <= 32 lists (K7c; utils/render_utils.py:441-456 with any number of actors: the background list and one
+ * list per actor): the same arguments and contract -- z / raw / rows / S HOST arrays of k entries, rows[l] nullable, ties: the earlier list
+ * first -- in a kernel of its own (csrc/merge_wide.hip: per-list state in LDS tables, not in unrolled registers).  Bit-identical to
+ * nm_merge_sorted list by list + nm_composite, and for k <= 4 to nm_merge_composite_lists.  The merged list lives in LDS only: at most 8014
+ * merged samples per ray (e.g. 320 + 31 x 192 = 6272); more, or k outside 1 .. 32, is refused with NM_ERR_ARG before anything is launched. */
+int nm_merge_composite_lists_wide(int k, const float* const* z, const float* const* raw, const int32_t* const* rows, const int* S, int64_t R,
+                                  const float* rays_d, int white_bkg, float* rgb, float* depth, float* acc, nm_stream_t stream);
+/* render_hybrid_nerf_multi_persons' per-batch body (utils/render_utils.py:390-456) for A >= 0 actors as one call: two-pass background of
+ * every ray (scalar bkg_near / bkg_far, :396-402); when precision_last != 0 the LAST background sample of every ray evaluated once more by
+ * the composited net at that NM_PREC_* (nm_mlp_forward_rays on z[:, -1:]; what the host mirror's mixed-precision policy does for the one
+ * sample whose interval ends on a placeholder; 0: not done); per actor a: near / far against verts[a] [V[a],3] (geo_threshold, :405-407),
+ * compaction of the hit rays -- ONE host read per actor: their count n_hit (the reference's boolean-mask indexing implies the same) --, the
+ * human pass of the hit rays through humans[a] / meshes[a] / T[a] into compact [n_hit + 1, S_human] arrays whose last row is the
+ * zero-density placeholder at far_z [S_human] (= the caller's torch.linspace(2 far, 3 far, S_human), :418-419), and a row index for every
+ * ray; then ONE merge + composite of the 1 + A lists (:441-456): nm_merge_composite_lists up to three actors, nm_merge_composite_lists_wide
+ * beyond -> rgb [R,3], depth [R].  humans / meshes / T / verts / V are HOST arrays of A entries (an actor may appear several times);
+ * t_vals [S], u [N], t_vals_human [S_human] = the caller's torch.linspace(0, 1, .).  All memory is the caller's workspace
+ * (nm_render_rays_multi_workspace_floats(R, S, N, S_human, A) floats: every ray may hit every actor).  A == 0 (background only), R == 0
+ * and an actor nobody hits are ordinary cases.  Shapes the merge cannot stage are refused before anything is enqueued.  Same kernels, same
+ * bits as the separate calls.  nm_render_rays_multi_live: as the *_live calls above -- the fine (or single) background pass and the human
+ * passes evaluate the colour head on their live samples only; live_ws holds the larger of R (S + N) and R S_human samples; rgb and depth
+ * are bit-identical. */
+int64_t nm_render_rays_multi_workspace_floats(int64_t R, int S, int N, int S_human, int A);
+int nm_render_rays_multi(nm_mlp_t coarse, nm_mlp_t fine, int A, const nm_mlp_t* humans, const nm_mesh_t* meshes, const double* const* T,
+                         const float* const* verts, const int* V, double geo_threshold, const float* origin, const float* direction, int64_t R,
+                         float bkg_near, float bkg_far, int S, int N, int S_human, const float* t_vals, const float* u, const float* t_vals_human,
+                         const float* far_z, int white_bkg, int precision_coarse, int precision_fine, int precision_last, int precision_human,
+                         float* workspace, float* rgb, float* depth, nm_stream_t stream);
+int nm_render_rays_multi_live(nm_mlp_t coarse, nm_mlp_t fine, int A, const nm_mlp_t* humans, const nm_mesh_t* meshes, const double* const* T,
+                              const float* const* verts, const int* V, double geo_threshold, const float* origin, const float* direction, int64_t R,
+                              float bkg_near, float bkg_far, int S, int N, int S_human, const float* t_vals, const float* u, const float* t_vals_human,
+                              const float* far_z, int white_bkg, int precision_coarse, int precision_fine, int precision_last, int precision_human,
+                              float* workspace, float* rgb, float* depth, void* live_ws, int64_t live_ws_bytes, int64_t chunk_samples,
+                              nm_stream_t stream);
 /* ONE KERNEL for the coarse tail of a two-pass render (utils/render_utils.py:139-147; ray_utils.py:138-194): the compositing weights of
  * raw [R,S,4] (raw2outputs), their inverse-CDF samples at u [N] and the sorted merge with z_vals -> z_out [R,S+N]; sigma is read once,
  * the weights are written only when weights_out [R,S] != NULL.  Bit-identical to nm_composite + nm_importance_z. */

@@ -17,6 +17,8 @@ inline hipStream_t as_stream(nm_stream_t s) { return reinterpret_cast<hipStream_
 // the net was created with the plain head (use_viewdirs=False): its whole-network output is (r, g, b, sigma) without a density-only form
 // at NM_PREC_I8X3 (mlp_host.hip)
 bool mlp_plain_head(nm_mlp_t mlp);
+// merge_wide.hip: the most merged samples per ray nm_merge_composite_lists_wide stages
+int wide_merge_max_samples();
 
 }  // namespace nm
 

@@ -328,4 +328,167 @@ int nm_render_rays_hybrid_live(nm_mlp_t coarse, nm_mlp_t fine, nm_mlp_t human, n
                               t_vals_human, white_bkg, precision_coarse, precision_fine, precision_human, workspace, rgb, depth, acc, stream);
 }
 
+// ---- render_hybrid_nerf_multi_persons' per-batch body (utils/render_utils.py:390-456) for A actors as one call: two-pass background of every
+// ray (:396-402), under the mixed precision policy the re-evaluation of every ray's LAST background sample (precision_last != 0: the sample
+// whose interval ends on an actor's placeholder, host mirror render_multi_rays), then per actor near / far against its posed body,
+// compaction of the hit rays (ONE host read per actor: their count -- the reference's boolean-mask indexing implies the same), the human
+// pass of the hit rays into COMPACT [n_hit + 1, S_human] arrays whose last row is the zero-density placeholder at far_z (:405-419) and a
+// row index for every ray, and ONE merge + composite kernel over the 1 + A lists (:441-456): nm_merge_composite_lists up to three actors,
+// nm_merge_composite_lists_wide beyond.  Built from the entry points above (and two row kernels of its own): same kernels, same bits as
+// calling them one by one.
+namespace {
+// dst[i * dst_stride + c] = src[i * src_stride + c], c < width: a column block of one row-major array into another
+__global__ __launch_bounds__(256) void strided_rows_kernel(const float* __restrict__ src, int64_t src_stride, float* __restrict__ dst, int64_t dst_stride,
+                                                           int width, int64_t n) {
+    const int64_t total = n * width;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = t / width;
+        const int c = (int)(t - i * width);
+        dst[i * dst_stride + c] = src[i * src_stride + c];
+    }
+}
+
+// rows[hit[i]] = i: the compact row of every hit ray (the others keep what the caller filled in: the placeholder row)
+__global__ __launch_bounds__(256) void hit_rows_kernel(const int32_t* __restrict__ hit, int64_t n_hit, int32_t* __restrict__ rows) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_hit; i += (int64_t)gridDim.x * blockDim.x) rows[hit[i]] = (int32_t)i;
+}
+
+inline int rows_grid(int64_t items) {
+    const int64_t b = (items + 255) / 256;
+    return (int)(b < 1 ? 1 : b > 4096 ? 4096 : b);
+}
+int copy_strided_rows(const float* src, int64_t src_stride, float* dst, int64_t dst_stride, int width, int64_t n, nm_stream_t stream) {
+    if (n <= 0) return NM_OK;
+    hipLaunchKernelGGL(strided_rows_kernel, dim3(rows_grid(n * width)), dim3(256), 0, nm::as_stream(stream), src, src_stride, dst, dst_stride, width, n);
+    return nm::check_launch("strided_rows_kernel");
+}
+int fill_hit_rows(const int32_t* hit, int64_t n_hit, int32_t* rows, nm_stream_t stream) {
+    if (n_hit <= 0) return NM_OK;
+    hipLaunchKernelGGL(hit_rows_kernel, dim3(rows_grid(n_hit)), dim3(256), 0, nm::as_stream(stream), hit, n_hit, rows);
+    return nm::check_launch("hit_rows_kernel");
+}
+
+struct MultiWs {
+    float *near_b, *far_b, *bkg_ws, *raw_b, *z_b, *z_last, *raw_last, *near_h, *far_h, *ho, *hd, *hn, *hf, *human_ws, *acc, *actors;
+    int32_t *hit, *counts, *cws;
+    int64_t raw_a, z_a, rows_a, per_actor, total;                 // an actor's block at actors + a * per_actor: raw | z | rows
+};
+inline MultiWs multi_layout(float* base, int64_t R, int S, int N, int Sh, int A) {
+    MultiWs w;
+    int64_t o = 0;
+    auto take = [&](int64_t n) { float* p = base ? base + o : nullptr; o += align4(n); return p; };
+    const int Sb = S + N;
+    w.near_b = take(R); w.far_b = take(R);
+    w.bkg_ws = take(nm_render_rays_bkg_workspace_floats(R, S, N));
+    w.raw_b = take(R * Sb * 4); w.z_b = take(R * Sb);
+    w.z_last = take(R); w.raw_last = take(R * 4);
+    w.near_h = take(R); w.far_h = take(R);
+    w.hit = reinterpret_cast<int32_t*>(take(R)); w.counts = reinterpret_cast<int32_t*>(take(4));
+    w.cws = reinterpret_cast<int32_t*>(take(nm_compact_workspace_ints(R)));
+    w.ho = take(R * 3); w.hd = take(R * 3); w.hn = take(R); w.hf = take(R);
+    w.human_ws = take(nm_render_rays_human_workspace_floats(R, Sh, 1));
+    w.acc = take(R);
+    w.raw_a = 0;                                                  // (every ray may hit every actor: n_hit + 1 <= R + 1 rows)
+    w.z_a = w.raw_a + align4((R + 1) * Sh * 4);
+    w.rows_a = w.z_a + align4((R + 1) * Sh);
+    w.per_actor = w.rows_a + align4(R);
+    w.actors = base ? base + o : nullptr;
+    o += (int64_t)A * w.per_actor;
+    w.total = o;
+    return w;
+}
+}  // namespace
+
+int64_t nm_render_rays_multi_workspace_floats(int64_t R, int S, int N, int S_human, int A) {
+    return multi_layout(nullptr, R < 0 ? 0 : R, S, N, S_human, A < 0 ? 0 : A).total;
+}
+
+static int render_rays_multi(const LiveWs* lw, nm_mlp_t coarse, nm_mlp_t fine, int A, const nm_mlp_t* humans, const nm_mesh_t* meshes, const double* const* T,
+                             const float* const* verts, const int* V, double geo_threshold, const float* origin, const float* direction, int64_t R,
+                             float bkg_near, float bkg_far, int S, int N, int S_human, const float* t_vals, const float* u, const float* t_vals_human,
+                             const float* far_z, int white_bkg, int precision_coarse, int precision_fine, int precision_last, int precision_human,
+                             float* workspace, float* rgb, float* depth, nm_stream_t stream) {
+    const char* who = lw ? "nm_render_rays_multi_live" : "nm_render_rays_multi";       // (one body, two entries: errors name the one that was called)
+    NM_REQUIRE(R >= 0 && S >= 1 && N >= 0 && S_human >= 2 && A >= 0 && A < 32, "%s: bad sizes (S=%d N=%d S_human=%d actors=%d, at most 31)", who, S, N, S_human, A);
+    NM_REQUIRE(R == 0 || (coarse && origin && direction && t_vals && workspace && rgb && depth), "%s: null pointer", who);
+    NM_REQUIRE(A == 0 || (humans && meshes && T && verts && V), "%s: null actor arrays", who);
+    NM_REQUIRE(R == 0 || A == 0 || (t_vals_human && far_z), "%s: null pointer", who);
+    for (int a = 0; a < A; ++a) NM_REQUIRE(R == 0 || (humans[a] && meshes[a] && T[a] && verts[a] && V[a] >= 1), "%s: actor %d has a null pointer or no vertices", who, a);
+    const int Sb = S + N;
+    const int64_t St = (int64_t)Sb + (int64_t)A * S_human;
+    if (A <= 3) NM_REQUIRE(St * 12 <= 64 * 1024, "%s: %lld merged samples exceed what nm_merge_composite_lists stages", who, (long long)St);
+    else NM_REQUIRE(St <= nm::wide_merge_max_samples(), "%s: %lld merged samples, nm_merge_composite_lists_wide stages at most %d", who, (long long)St,
+                    nm::wide_merge_max_samples());
+    if (R == 0) return NM_OK;
+    hipStream_t st = nm::as_stream(stream);
+    const MultiWs w = multi_layout(workspace, R, S, N, S_human, A);
+    int rc;
+    union { float f; uint32_t u; } nb{bkg_near}, fb{bkg_far};
+    if ((rc = nm::check_hip(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w.near_b), (int)nb.u, (size_t)R, st), (std::string(who) + ": near").c_str()))) return rc;
+    if ((rc = nm::check_hip(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(w.far_b), (int)fb.u, (size_t)R, st), (std::string(who) + ": far").c_str()))) return rc;
+    if ((rc = render_rays_bkg(lw, coarse, fine, origin, direction, w.near_b, w.far_b, R, S, N, t_vals, u, white_bkg, precision_coarse, precision_fine, w.bkg_ws,
+                              w.raw_b, w.z_b, nullptr, nullptr, nullptr, stream))) return rc;
+    if (precision_last) {                                         // z[:, -1:] -> forward_rays -> raw[:, -1, :]
+        if ((rc = copy_strided_rows(w.z_b + (Sb - 1), Sb, w.z_last, 1, 1, R, stream))) return rc;
+        if ((rc = nm_mlp_forward_rays(fine ? fine : coarse, origin, direction, w.z_last, R, 1, precision_last, 1.f, w.raw_last, stream))) return rc;
+        if ((rc = copy_strided_rows(w.raw_last, 4, w.raw_b + (int64_t)(Sb - 1) * 4, (int64_t)Sb * 4, 4, R, stream))) return rc;
+    }
+    const float* zs[32];
+    const float* raws[32];
+    const int32_t* rows[32];
+    int Ss[32];
+    zs[0] = w.z_b; raws[0] = w.raw_b; rows[0] = nullptr; Ss[0] = Sb;
+    for (int a = 0; a < A; ++a) {
+        float* h_raw = w.actors + a * w.per_actor + w.raw_a;
+        float* h_z = w.actors + a * w.per_actor + w.z_a;
+        int32_t* h_rows = reinterpret_cast<int32_t*>(w.actors + a * w.per_actor + w.rows_a);
+        if ((rc = nm_near_far(origin, direction, R, verts[a], V[a], geo_threshold, w.near_h, w.far_h, stream))) return rc;
+        if ((rc = nm_compact_hits(w.near_h, w.far_h, R, w.hit, nullptr, w.counts, w.cws, stream))) return rc;
+        int32_t n_hit = 0;
+        if ((rc = nm::check_hip(hipMemcpyAsync(&n_hit, w.counts, 4, hipMemcpyDeviceToHost, st), (std::string(who) + ": hit count").c_str()))) return rc;
+        if ((rc = nm::check_hip(hipStreamSynchronize(st), (std::string(who) + ": hit count").c_str()))) return rc;
+        NM_REQUIRE(n_hit >= 0 && n_hit <= R, "%s: actor %d: hit count %d of %lld rays", who, a, (int)n_hit, (long long)R);
+        // the placeholder row behind the hit rays' rows, and every ray pointing at it until it is found among the hits
+        if ((rc = nm::check_hip(hipMemcpyAsync(h_z + (int64_t)n_hit * S_human, far_z, (size_t)S_human * 4, hipMemcpyDeviceToDevice, st),
+                                (std::string(who) + ": placeholder z").c_str()))) return rc;
+        if ((rc = nm::check_hip(hipMemsetAsync(h_raw + (int64_t)n_hit * S_human * 4, 0, (size_t)S_human * 16, st), (std::string(who) + ": placeholder raw").c_str())))
+            return rc;
+        if ((rc = nm::check_hip(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h_rows), (int)n_hit, (size_t)R, st), (std::string(who) + ": rows").c_str()))) return rc;
+        if (n_hit > 0) {
+            if ((rc = nm_gather_rows(origin, w.hit, nullptr, n_hit, 3, w.ho, stream))) return rc;
+            if ((rc = nm_gather_rows(direction, w.hit, nullptr, n_hit, 3, w.hd, stream))) return rc;
+            if ((rc = nm_gather_rows(w.near_h, w.hit, nullptr, n_hit, 1, w.hn, stream))) return rc;
+            if ((rc = nm_gather_rows(w.far_h, w.hit, nullptr, n_hit, 1, w.hf, stream))) return rc;
+            if ((rc = render_rays_human(lw, humans[a], meshes[a], T[a], w.ho, w.hd, w.hn, w.hf, n_hit, S_human, t_vals_human, white_bkg, 1.f, precision_human,
+                                        w.human_ws, h_raw, h_z, nullptr, nullptr, nullptr, stream))) return rc;
+            if ((rc = fill_hit_rows(w.hit, n_hit, h_rows, stream))) return rc;
+        }
+        zs[1 + a] = h_z; raws[1 + a] = h_raw; rows[1 + a] = h_rows; Ss[1 + a] = S_human;
+    }
+    if (A <= 3) return nm_merge_composite_lists(1 + A, zs, raws, rows, Ss, R, direction, white_bkg, rgb, depth, w.acc, stream);
+    return nm_merge_composite_lists_wide(1 + A, zs, raws, rows, Ss, R, direction, white_bkg, rgb, depth, w.acc, stream);
+}
+
+int nm_render_rays_multi(nm_mlp_t coarse, nm_mlp_t fine, int A, const nm_mlp_t* humans, const nm_mesh_t* meshes, const double* const* T,
+                         const float* const* verts, const int* V, double geo_threshold, const float* origin, const float* direction, int64_t R,
+                         float bkg_near, float bkg_far, int S, int N, int S_human, const float* t_vals, const float* u, const float* t_vals_human,
+                         const float* far_z, int white_bkg, int precision_coarse, int precision_fine, int precision_last, int precision_human,
+                         float* workspace, float* rgb, float* depth, nm_stream_t stream) {
+    return render_rays_multi(nullptr, coarse, fine, A, humans, meshes, T, verts, V, geo_threshold, origin, direction, R, bkg_near, bkg_far, S, N, S_human, t_vals, u,
+                             t_vals_human, far_z, white_bkg, precision_coarse, precision_fine, precision_last, precision_human, workspace, rgb, depth, stream);
+}
+
+int nm_render_rays_multi_live(nm_mlp_t coarse, nm_mlp_t fine, int A, const nm_mlp_t* humans, const nm_mesh_t* meshes, const double* const* T,
+                              const float* const* verts, const int* V, double geo_threshold, const float* origin, const float* direction, int64_t R,
+                              float bkg_near, float bkg_far, int S, int N, int S_human, const float* t_vals, const float* u, const float* t_vals_human,
+                              const float* far_z, int white_bkg, int precision_coarse, int precision_fine, int precision_last, int precision_human,
+                              float* workspace, float* rgb, float* depth, void* live_ws, int64_t live_ws_bytes, int64_t chunk_samples, nm_stream_t stream) {
+    NM_REQUIRE(S >= 1 && N >= 0 && S_human >= 2, "nm_render_rays_multi_live: bad sizes");
+    NM_LIVE_WS_REQUIRE("nm_render_rays_multi_live", fine ? precision_fine : precision_coarse, R * (int64_t)(S + N), S + N);      // the composited passes
+    if (A > 0) { NM_LIVE_WS_REQUIRE("nm_render_rays_multi_live", precision_human, R * (int64_t)S_human, S_human); }              // share live_ws
+    const LiveWs lw{live_ws, live_ws_bytes, chunk_samples};
+    return render_rays_multi(&lw, coarse, fine, A, humans, meshes, T, verts, V, geo_threshold, origin, direction, R, bkg_near, bkg_far, S, N, S_human, t_vals, u,
+                             t_vals_human, far_z, white_bkg, precision_coarse, precision_fine, precision_last, precision_human, workspace, rgb, depth, stream);
+}
+
 }  // extern "C"

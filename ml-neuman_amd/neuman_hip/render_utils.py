@@ -38,6 +38,15 @@ TERMINATION_CHUNK = int(os.environ.get("NEUMAN_TERMINATION_CHUNK", "32"))
 TERMINATION_COARSE = float(os.environ.get("NEUMAN_TERMINATION_COARSE", "4e-13"))
 TERMINATION_MIN_CHUNK = 16
 FUSED_HYBRID_RAYS = int(os.environ.get("NEUMAN_FUSED_HYBRID_RAYS", 1 << 17))
+# The multi-person renderer's batch body as ONE C call (render_multi_rays_fused: nm_render_rays_multi, any number of actors merged and composited
+# by one kernel), in batches of FUSED_MULTI_RAYS rays.  Bit-identical to the step-by-step body and tested.  Off by default: measured on the 1080p
+# frame (profiles/multi_fused.md) it is 2-4 % slower than today's route at 4-14 x less peak memory, and the rule of profiles/live_heads.md admits a
+# route as a default only on a measured gain.  NEUMAN_MULTI_FUSED=1 turns it on.
+MULTI_FUSED = os.environ.get("NEUMAN_MULTI_FUSED", "0") == "1"
+FUSED_MULTI_RAYS = int(os.environ.get("NEUMAN_FUSED_MULTI_RAYS", 1 << 17))
+MERGE_MAX_SAMPLES = (64 * 1024) // 12            # merged samples per ray nm_merge_composite_lists stages in LDS (csrc/ray_ops.hip) ...
+WIDE_MERGE_MAX_SAMPLES = 8014                    # ... and nm_merge_composite_lists_wide (csrc/merge_wide.hip, kWideMaxSamples)
+WIDE_MERGE_MAX_LISTS = 32
 # The colour head on live samples only (vanilla.Joiner role='composite': nm_mlp_forward_*_live, nm_render_rays_*_live) in every composited pass
 # of render_smpl_nerf, render_hybrid_nerf and render_hybrid_nerf_multi_persons, and in render_vanilla's gridded, marched and single-net passes.
 # Off: those passes run the whole network on every sample they evaluate (frames are bit-identical either way).  render_vanilla's plain path takes
@@ -540,6 +549,33 @@ def merge_composite_lists(z_lists, raw_lists, rays_d, white_bkg=True, rows=None)
     return rgb, depth, acc
 
 
+def merge_composite_lists_wide(z_lists, raw_lists, rays_d, white_bkg=True, rows=None):
+    """merge_composite_lists for 1 .. 32 lists (nm_merge_composite_lists_wide, K7c: the background and any number of actors in ONE kernel, the
+    merged list never in HBM; at most WIDE_MERGE_MAX_SAMPLES merged samples per ray).  Same arguments, same result: bit-identical to
+    merge_sorted list by list + raw2outputs, and up to four lists to merge_composite_lists."""
+    _lib.require_gpu()
+    k = len(z_lists)
+    R = rays_d.shape[0]
+    dev = rays_d.device
+    if not 1 <= k <= WIDE_MERGE_MAX_LISTS or len(raw_lists) != k:
+        raise _lib.NeumanHipError(f"merge_composite_lists_wide: 1 <= k <= {WIDE_MERGE_MAX_LISTS} lists with their records (k={k})")
+    zs = [z.to(torch.float32).contiguous() for z in z_lists]
+    raws = [r_.to(torch.float32).contiguous() for r_ in raw_lists]
+    rows = [None] * k if rows is None else [None if x is None else x.to(torch.int32).contiguous() for x in rows]
+    for l_ in range(k):
+        if rows[l_] is None and zs[l_].shape[0] != R:
+            raise _lib.NeumanHipError(f"merge_composite_lists_wide: list {l_} has {zs[l_].shape[0]} rows for {R} rays")
+    arr = ctypes.c_void_p * k
+    rgb = torch.empty((R, 3), device=dev, dtype=torch.float32)
+    depth = torch.empty(R, device=dev, dtype=torch.float32)
+    acc = torch.empty(R, device=dev, dtype=torch.float32)
+    _lib.check(_lib.lib().nm_merge_composite_lists_wide(
+        k, arr(*[z.data_ptr() for z in zs]), arr(*[r_.data_ptr() for r_ in raws]), arr(*[None if x is None else x.data_ptr() for x in rows]),
+        (ctypes.c_int * k)(*[int(z.shape[1]) for z in zs]), R, _lib.dev_ptr(rays_d.contiguous()), int(bool(white_bkg)), _lib.dev_ptr(rgb), _lib.dev_ptr(depth),
+        _lib.dev_ptr(acc), _lib.stream_ptr()), "nm_merge_composite_lists_wide")
+    return rgb, depth, acc
+
+
 def render_smpl_nerf_rays(human_net, o, d, posed_verts, mesh, samples_per_ray, white_bkg=True, render_can=False,
                           geo_threshold=DEFAULT_GEO_THRESH, interval_comp=1.0, precision=None, trace=None, given=None):
     """Device core of render_smpl_nerf -> (rgb [R,3], depth [R], acc [R]) CUDA.  `given`: see bkg_pass_rays."""
@@ -707,6 +743,70 @@ def render_hybrid_rays_fused(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bk
     return rgb, depth, acc
 
 
+def multi_merge_stages(n_actors, samples_per_ray, importance_samples_per_ray):
+    """Can the one-kernel merge of render_multi_rays_fused stage the background list and `n_actors` actor lists of these sizes?  (Up to three
+    actors: nm_merge_composite_lists; beyond: nm_merge_composite_lists_wide.)"""
+    total = int(samples_per_ray) + int(importance_samples_per_ray) + int(n_actors) * int(samples_per_ray)
+    if n_actors <= 3:
+        return total <= MERGE_MAX_SAMPLES
+    return 1 + n_actors <= WIDE_MERGE_MAX_LISTS and total <= WIDE_MERGE_MAX_SAMPLES
+
+
+def render_multi_rays_fused(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far, posed_verts, meshes, samples_per_ray,
+                            importance_samples_per_ray, white_bkg=True, geo_threshold=DEFAULT_GEO_THRESH, precision=None, live=None):
+    """render_multi_rays' batch body as ONE C call per batch (nm_render_rays_multi; render_utils.py:390-456) for any number of actors:
+    same kernels up to the merge, same bits; no trace / replay / early termination hooks -- the plain path of a frame render.  With more than
+    three actors the lists are merged and composited by ONE kernel (nm_merge_composite_lists_wide) from compact per-actor arrays, instead of
+    full [rays, S] arrays merged list by list through HBM.  live (default: LIVE_HEADS): nm_render_rays_multi_live, as render_hybrid_rays_fused.
+    -> (rgb [R,3], depth [R])"""
+    _lib.require_gpu()
+    R = o.shape[0]
+    dev = o.device
+    A = len(human_nets)
+    rgb = torch.empty((R, 3), device=dev, dtype=torch.float32)
+    depth = torch.empty(R, device=dev, dtype=torch.float32)
+    S, N, Sh = int(samples_per_ray), int(importance_samples_per_ray) if fine_bkg is not None else 0, int(samples_per_ray)
+    if not multi_merge_stages(A, S, N):
+        raise _lib.NeumanHipError(f"render_multi_rays_fused: {S + N} + {A} x {Sh} merged samples exceed what the one-kernel merge stages")
+    verts = [v.to(dev, torch.float32).contiguous() for v in posed_verts]
+    t_vals = torch.linspace(0., 1., steps=S, device=dev)
+    u = torch.linspace(0., 1., steps=N, device=dev) if N else None
+    far_z = torch.linspace(float(bkg_far) * 2, float(bkg_far) * 3, samples_per_ray, device=dev)        # :418-419
+    # the C call sizes every actor's compact arrays for all rays of the batch (the hit counts are only known inside): batches of
+    # FUSED_MULTI_RAYS rays and ONE workspace
+    step = max(1, min(MAX_RAYS_PER_LAUNCH, FUSED_MULTI_RAYS))
+    ws = _ws(_lib.lib().nm_render_rays_multi_workspace_floats(min(R, step), S, N, Sh, A), dev)
+    last_net = fine_bkg if fine_bkg is not None else coarse_bkg
+    precs = (coarse_bkg._prec(precision, None if fine_bkg is not None else 'shading'), fine_bkg._prec(precision, 'shading') if fine_bkg is not None else 0,
+             human_nets[0]._prec(precision, 'shading') if A else 0)
+    for h in human_nets[1:]:
+        if h._prec(precision, 'shading') != precs[2]:
+            raise _lib.NeumanHipError("render_multi_rays_fused: the actors' nets run at one precision")
+    # the mixed policy's re-evaluation of every ray's last background sample (render_multi_rays)
+    prec_last = _lib.PRECISIONS['fp16x3'] if (last_net._prec(precision, 'shading') == _lib.NM_PREC_I8X3 and (precision or last_net.precision) == 'mixed') else 0
+    n_live = min(R, step) * max(S + N, Sh if A else 0)
+    live = (LIVE_HEADS if live is None else bool(live)) and n_live >= vanilla.LIVE_MIN_SAMPLES and _lib.NM_PREC_I8X3 in (precs[1] if N else precs[0], precs[2])
+    lws, lbytes = vanilla.live_workspace_for(n_live, 0, dev) if live else (None, 0)
+    tail = (_lib.dev_ptr(lws, torch.uint8), lbytes, 0, _lib.stream_ptr()) if live else (_lib.stream_ptr(),)
+    entry = _lib.lib().nm_render_rays_multi_live if live else _lib.lib().nm_render_rays_multi
+    arr = ctypes.c_void_p * max(A, 1)
+    humans = arr(*[h.handle() for h in human_nets]) if A else None
+    mesh_h = arr(*[m.handle for m in meshes]) if A else None
+    Ts = arr(*[_lib.dev_ptr(m.T, torch.float64, 'T') for m in meshes]) if A else None
+    vs = arr(*[v.data_ptr() for v in verts]) if A else None
+    Vs = (ctypes.c_int * max(A, 1))(*[int(v.shape[0]) for v in verts]) if A else None
+    for i in range(0, R, step):
+        j = min(i + step, R)
+        oc, dc = o[i:j].contiguous(), d[i:j].contiguous()
+        r_, d_ = rgb[i:j], depth[i:j]
+        _lib.check(entry(
+            coarse_bkg.handle(), fine_bkg.handle() if fine_bkg is not None else None, A, humans, mesh_h, Ts, vs, Vs, float(geo_threshold), _lib.dev_ptr(oc),
+            _lib.dev_ptr(dc), j - i, float(bkg_near), float(bkg_far), S, N, Sh, _lib.dev_ptr(t_vals), _lib.dev_ptr(u), _lib.dev_ptr(t_vals), _lib.dev_ptr(far_z),
+            int(bool(white_bkg)), precs[0], precs[1], prec_last, precs[2], _lib.dev_ptr(ws), _lib.dev_ptr(r_), _lib.dev_ptr(d_), *tail),
+            "nm_render_rays_multi_live" if live else "nm_render_rays_multi")
+    return rgb, depth
+
+
 def render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far, posed_verts, meshes, samples_per_ray,
                       importance_samples_per_ray, white_bkg=True, geo_threshold=DEFAULT_GEO_THRESH, precision=None, trace=None,
                       given=None):
@@ -724,6 +824,12 @@ def render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far,
 
 def _render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far, posed_verts, meshes, samples_per_ray, importance_samples_per_ray, white_bkg,
                        geo_threshold, precision, trace, given):
+    if (MULTI_FUSED and TERMINATION_EPS <= 0 and trace is None and given is None and not _occupancy_on(coarse_bkg, fine_bkg)
+            and all(occupancy.grid_of(h_) is None for h_ in human_nets)
+            and len({h_._prec(precision, 'shading') for h_ in human_nets}) <= 1                   # (the call takes ONE precision for the actors' nets)
+            and multi_merge_stages(len(human_nets), samples_per_ray, importance_samples_per_ray if fine_bkg is not None else 0)):
+        return render_multi_rays_fused(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far, posed_verts, meshes, samples_per_ray,
+                                       importance_samples_per_ray, white_bkg, geo_threshold, precision)
     R = o.shape[0]
     rgb = torch.empty((R, 3), device=o.device, dtype=torch.float32)
     depth = torch.empty(R, device=o.device, dtype=torch.float32)
