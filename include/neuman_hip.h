@@ -299,6 +299,14 @@ int nm_mlp_sigma_ray_chunk(nm_mlp_t mlp, const float* origin, const float* direc
  * nm_occ_compact_samples: sample_idx [R*S] receives the ascending flat indices r*S + s of the samples of rays origin + direction *
  *   z_vals [R,S] (the point built as the MLP launches build it) whose cell is occupied or that lie outside the box; counts[0] =
  *   their number, counts[1] = the skipped (device int32[2]).  workspace: nm_occ_compact_workspace_ints(R*S) int32.
+ * nm_occ_compact_ray_chunk: nm_occ_compact_samples for one chunk of a front-to-back march (nm_mlp_forward_ray_chunk's arguments): the
+ *   live rays are n = n_rays_dev ? clamp(*n_rays_dev, 0, n_rays) : n_rays, read on the device (n_rays only sizes the launch); candidate
+ *   j in [0, n*S) is sample s = s0 + j % S of ray r = ray_idx ? ray_idx[j / S] : j / S (entries of ray_idx at or past n are never read;
+ *   without ray_idx n_rays <= R).  sample_idx [n_rays*S] receives the flat indices r * S_total + s of the candidates whose cell is
+ *   occupied or that lie outside the box -- the same test on the same point, so the same decision as nm_occ_compact_samples' -- in
+ *   candidate order (ascending when ray_idx is); counts = (kept, n*S - kept).  What nm_mlp_forward_samples, nm_mlp_sigma_samples and
+ *   nm_mlp_forward_samples_live take.  0 <= s0, 1 <= S, s0 + S <= S_total; R * S_total and n_rays * S below 2^31; n_rays == 0 writes
+ *   counts = (0, 0).  workspace: nm_occ_compact_workspace_ints(n_rays * S) int32.  No host synchronisation, no allocation.
  * nm_mlp_forward_samples / nm_mlp_sigma_samples: nm_mlp_forward_rays / nm_mlp_sigma_rays on the listed samples only (in_mode 3):
  *   the first *n_dev entries of sample_idx (n_dev nullable: n_max entries; n_max = the list's upper bound) are evaluated and written
  *   into out[r, s] [R,S,4]; nothing else of out is touched.  Bit-identical to the matching records of the every-sample launch.
@@ -311,6 +319,9 @@ int nm_occ_build(nm_mlp_t mlp, const float* aabb, int res, int probes, int dilat
 int64_t nm_occ_compact_workspace_ints(int64_t n_samples);
 int nm_occ_compact_samples(const uint32_t* bits, int res, const float* aabb, const float* origin, const float* direction, const float* z_vals,
                            int64_t R, int S, int32_t* sample_idx, int32_t* counts, int32_t* workspace, nm_stream_t stream);
+int nm_occ_compact_ray_chunk(const uint32_t* bits, int res, const float* aabb, const float* origin, const float* direction, const float* z_vals,
+                             int64_t R, int S_total, const int32_t* ray_idx, const int32_t* n_rays_dev, int64_t n_rays, int s0, int S,
+                             int32_t* sample_idx, int32_t* counts, int32_t* workspace, nm_stream_t stream);
 int nm_mlp_forward_samples(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S,
                            const int32_t* sample_idx, const int32_t* n_dev, int64_t n_max, int precision, float sigma_scale, float* out,
                            nm_stream_t stream);

@@ -9,6 +9,11 @@
 //     box), ascending, and their count -- both on the device: wave ballot + popcount prefix, a two-level scan (nearfar.hip's scheme, K2b).
 //   * nm_occ_compact_points (K11b): the same for the points of an [n,3] array -- the warped canonical points of a posed human pass; the
 //     same cell test and scan, only the point source differs.
+//   * nm_occ_compact_ray_chunk: the same for ONE CHUNK of a front-to-back march (march.hip, render_utils.march_pass_rays): samples
+//     s0 .. s0+S-1 of the rays a live list names, the list's length read on the device -- the flat indices r * S_total + s of the occupied ones,
+//     in candidate order (ascending when the list is).  The same cell test on the same point, so a sample's decision is the bit
+//     nm_occ_compact_samples makes for it: early ray termination and the grid work together (a skipped sample keeps raw = 0, the factor
+//     1 - 0 + 1e-10 in the running transmittance, what the march already handles for relu(sigma) = 0).
 //   * nm_mlp_forward_samples / nm_mlp_sigma_samples (mlp_host.hip, in_mode 3 of mlp_device.h) evaluate the listed samples only,
 //     nm_mlp_forward_listed (in_mode 4) the listed points.
 //
@@ -134,6 +139,8 @@ struct SamplePoints {
     const float* direction;
     const float* z;
     int S;
+    __device__ __forceinline__ int64_t limit(int64_t n) const { return n; }
+    __device__ __forceinline__ int32_t index(int64_t i) const { return (int32_t)i; }
     __device__ __forceinline__ void point(int64_t i, float (&p)[3]) const {
         const int64_t r = i / S;
         const float zz = z[i];
@@ -147,6 +154,8 @@ struct SamplePoints {
 // ... or point i of an [n,3] array (the warped canonical points of a posed human pass)
 struct GivenPoints {
     const float* pts;
+    __device__ __forceinline__ int64_t limit(int64_t n) const { return n; }
+    __device__ __forceinline__ int32_t index(int64_t i) const { return (int32_t)i; }
     __device__ __forceinline__ void point(int64_t i, float (&p)[3]) const {
         p[0] = pts[i * 3];
         p[1] = pts[i * 3 + 1];
@@ -154,9 +163,41 @@ struct GivenPoints {
     }
 };
 
+// ... or candidate j of a march's chunk: sample s0 + j % S of the (j / S)-th ray of a live list whose length *n_rays_dev stays on the
+// device (nullable: n_rays; ray_idx nullable: rays 0 .. n-1).  Only the first n entries of ray_idx are read: the march's lists are
+// uninitialised beyond their count.  Consecutive candidates are consecutive samples of a ray: z is read coalesced along s.  Every count
+// fits an int (the entry checks n_rays * S and R * S_total < 2^31).
+__device__ __forceinline__ int live_rays(const int32_t* __restrict__ n_rays_dev, int n_rays) {
+    return n_rays_dev ? min(max(*n_rays_dev, 0), n_rays) : n_rays;
+}
+struct ChunkPoints {
+    const float* origin;
+    const float* direction;
+    const float* z;
+    const int32_t* ray_idx;
+    const int32_t* n_rays_dev;
+    int n_rays, S_total, s0, S;
+    __device__ __forceinline__ int64_t limit(int64_t) const { return (int64_t)live_rays(n_rays_dev, n_rays) * S; }
+    __device__ __forceinline__ int32_t index(int64_t j) const {
+        const int k = (int)j / S;
+        const int r = ray_idx ? ray_idx[k] : k;
+        return r * S_total + s0 + ((int)j - k * S);
+    }
+    __device__ __forceinline__ void point(int64_t j, float (&p)[3]) const {
+        const int i = index(j);
+        const int r = i / S_total;
+        const float zz = z[i];
+        const float* o = origin + (int64_t)r * 3;
+        const float* d = direction + (int64_t)r * 3;
+        p[0] = o[0] + d[0] * zz;
+        p[1] = o[1] + d[1] * zz;
+        p[2] = o[2] + d[2] * zz;
+    }
+};
+
 template <class Src>
 __device__ __forceinline__ bool listed(const OccBox& B, const uint32_t* __restrict__ bits, const Src& src, int64_t i, int64_t n) {
-    if (i >= n) return false;
+    if (i >= src.limit(n)) return false;
     float p[3];
     src.point(i, p);
     return point_occupied(B, bits, p);
@@ -179,8 +220,10 @@ __global__ __launch_bounds__(kOccBlock) void occ_count_kernel(const OccBox B, co
     }
 }
 
-// pass 2: exclusive scan of the block counts (one block); counts[0] = occupied, counts[1] = skipped
-__global__ __launch_bounds__(1024) void occ_scan_kernel(int32_t* __restrict__ block_counts, int nblocks, int64_t n, int32_t* __restrict__ counts) {
+// pass 2: exclusive scan of the block counts (one block); counts[0] = occupied, counts[1] = skipped of n points -- or, for a march's
+// chunk (per_ray > 0), of live_rays(n_rays_dev, n_rays) * per_ray candidates
+__global__ __launch_bounds__(1024) void occ_scan_kernel(int32_t* __restrict__ block_counts, int nblocks, int64_t n, const int32_t* __restrict__ n_rays_dev,
+                                                        int n_rays, int per_ray, int32_t* __restrict__ counts) {
     __shared__ int wave_tot[16];
     __shared__ int carry_s;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -206,6 +249,7 @@ __global__ __launch_bounds__(1024) void occ_scan_kernel(int32_t* __restrict__ bl
         __syncthreads();
     }
     if (threadIdx.x == 0) {
+        if (per_ray > 0) n = (int64_t)live_rays(n_rays_dev, n_rays) * per_ray;
         counts[0] = carry_s;
         counts[1] = (int32_t)(n - carry_s);
     }
@@ -224,7 +268,7 @@ __global__ __launch_bounds__(kOccBlock) void occ_write_kernel(const OccBox B, co
     __syncthreads();
     int woff = 0;
     for (int w = 0; w < wid; ++w) woff += wave_cnt[w];
-    if (occ) idx[block_offsets[blockIdx.x] + woff + __popcll(b & ((1ull << lane) - 1ull))] = (int32_t)i;
+    if (occ) idx[block_offsets[blockIdx.x] + woff + __popcll(b & ((1ull << lane) - 1ull))] = src.index(i);
 }
 
 bool box_ok(const float* aabb) {
@@ -236,7 +280,7 @@ bool box_ok(const float* aabb) {
 // the three passes: count per block, scan (counts = (kept, skipped)), write -- the count stays on the device
 template <class Src>
 int occ_compact(const char* what, const uint32_t* bits, int res, const float* aabb, const Src& src, int64_t n, int32_t* idx, int32_t* counts,
-                int32_t* workspace, hipStream_t st) {
+                int32_t* workspace, hipStream_t st, const int32_t* n_rays_dev = nullptr, int n_rays = 0, int per_ray = 0) {
     OccBox B;
     for (int a = 0; a < 3; ++a) {
         B.lo[a] = aabb[a];
@@ -248,7 +292,7 @@ int occ_compact(const char* what, const uint32_t* bits, int res, const float* aa
         hipLaunchKernelGGL(occ_count_kernel<Src>, dim3(nblocks), dim3(kOccBlock), 0, st, B, bits, src, n, workspace);
         if (int e = nm::check_launch("occ_count_kernel")) return e;
     }
-    hipLaunchKernelGGL(occ_scan_kernel, dim3(1), dim3(1024), 0, st, workspace, nblocks, n, counts);
+    hipLaunchKernelGGL(occ_scan_kernel, dim3(1), dim3(1024), 0, st, workspace, nblocks, n, n_rays_dev, n_rays, per_ray, counts);
     if (int e = nm::check_launch("occ_scan_kernel")) return e;
     if (nblocks > 0) {
         hipLaunchKernelGGL(occ_write_kernel<Src>, dim3(nblocks), dim3(kOccBlock), 0, st, B, bits, src, n, workspace, idx);
@@ -350,6 +394,22 @@ int nm_occ_compact_points(const uint32_t* bits, int res, const float* aabb, cons
     NM_REQUIRE(n >= 0 && n < (1ll << 31), "nm_occ_compact_points: bad size (n=%lld)", (long long)n);
     NM_REQUIRE(box_ok(aabb), "nm_occ_compact_points: the box must have finite lo < hi on every axis");
     return occ_compact("nm_occ_compact_points", bits, res, aabb, GivenPoints{pts}, n, point_idx, counts, workspace, nm::as_stream(stream));
+}
+
+int nm_occ_compact_ray_chunk(const uint32_t* bits, int res, const float* aabb, const float* origin, const float* direction, const float* z_vals,
+                             int64_t R, int S_total, const int32_t* ray_idx, const int32_t* n_rays_dev, int64_t n_rays, int s0, int S,
+                             int32_t* sample_idx, int32_t* counts, int32_t* workspace, nm_stream_t stream) {
+    NM_REQUIRE(bits && aabb && counts && workspace, "nm_occ_compact_ray_chunk: null pointer");
+    NM_REQUIRE(n_rays == 0 || (origin && direction && z_vals && sample_idx), "nm_occ_compact_ray_chunk: null pointer");
+    NM_REQUIRE(res >= 4 && res <= 256 && res % 4 == 0, "nm_occ_compact_ray_chunk: res %d outside 4..256 or not a multiple of 4", res);
+    NM_REQUIRE(box_ok(aabb), "nm_occ_compact_ray_chunk: the box must have finite lo < hi on every axis");
+    NM_REQUIRE(S >= 1 && s0 >= 0 && (int64_t)s0 + S <= S_total, "nm_occ_compact_ray_chunk: bad chunk (s0=%d S=%d S_total=%d)", s0, S, S_total);
+    NM_REQUIRE(R >= 0 && n_rays >= 0 && R * (int64_t)S_total < (1ll << 31) && n_rays * (int64_t)S < (1ll << 31),
+               "nm_occ_compact_ray_chunk: bad sizes (R=%lld S_total=%d n_rays=%lld S=%d)", (long long)R, S_total, (long long)n_rays, S);
+    NM_REQUIRE(ray_idx || n_rays <= R, "nm_occ_compact_ray_chunk: %lld rays listed without ray_idx, %lld given", (long long)n_rays, (long long)R);
+    return occ_compact("nm_occ_compact_ray_chunk", bits, res, aabb,
+                       ChunkPoints{origin, direction, z_vals, ray_idx, n_rays_dev, (int)n_rays, S_total, s0, S}, n_rays * (int64_t)S, sample_idx, counts,
+                       workspace, nm::as_stream(stream), n_rays_dev, (int)n_rays, S);
 }
 
 }  // extern "C"

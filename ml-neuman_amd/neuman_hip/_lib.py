@@ -45,6 +45,7 @@ SIGNATURES = {
     "nm_occ_build": (i32, [ctypes.c_void_p, ctypes.c_void_p, i32, i32, i32, ctypes.c_float, i32, i32, c_f32p, i64, c_i32p, c_stream]),
     "nm_occ_compact_workspace_ints": (i64, [i64]),
     "nm_occ_compact_samples": (i32, [c_i32p, i32, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, c_i32p, c_i32p, c_i32p, c_stream]),
+    "nm_occ_compact_ray_chunk": (i32, [c_i32p, i32, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, c_i32p, c_i32p, i64, i32, i32, c_i32p, c_i32p, c_i32p, c_stream]),
     "nm_mlp_forward_samples": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, c_i32p, c_i32p, i64, i32, ctypes.c_float, c_f32p, c_stream]),
     "nm_mlp_sigma_samples": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, c_i32p, c_i32p, i64, i32, ctypes.c_float, c_f32p, c_stream]),
     "nm_occ_compact_points": (i32, [c_i32p, i32, ctypes.c_void_p, c_f32p, i64, c_i32p, c_i32p, c_i32p, c_stream]),

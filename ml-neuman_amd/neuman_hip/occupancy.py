@@ -24,6 +24,12 @@ A gridded pass whose raw is composited and nothing else (role='composite': rende
 leaves the colour head to the evaluated samples that have density: forward_rays / forward_points run nm_mlp_forward_samples_live /
 nm_mlp_forward_listed_live, the fused human pass nm_render_rays_human_occ_live; the frame is bit-identical.
 
+Together with early ray termination (render_utils.MARCH_WITH_GRID, NEUMAN_MARCH_WITH_GRID=1; off by default, and then the combination is
+refused as before): the marched background passes (render_utils.march_pass_rays with grid=) list, chunk by chunk, the occupied samples of the
+LIVE rays only (OccupancyGrid.compact_ray_chunk: nm_occ_compact_ray_chunk -- the same cell test on the same point as `compact`, so every
+sample's decision is the same bit) and evaluate that list into the march's raw (forward_listed_samples); a skipped sample keeps raw = 0,
+the factor 1 - 0 + 1e-10 of the running transmittance, which the march already handles for relu(sigma) = 0.
+
 Training never consults a grid: the trainers evaluate their nets through the training forward (Joiner.forward in train() mode,
 neuman_hip/train.py) on the points of the batch, which knows nothing of grids -- a human-trainer step is the same with or without
 one (tests/test_hip_occupancy_human.py).  Rebuild the grid (from_net) after training has moved the density.
@@ -205,6 +211,29 @@ class OccupancyGrid:
         return idx, counts
 
 
+    def compact_ray_chunk(self, o, d, z, ray_idx, n_rays_dev, s0, c, n_rays=None):
+        """The occupied samples among samples s0 .. s0+c-1 of the live rays of a march (nm_occ_compact_ray_chunk): ray_idx int32 (only its
+        first *n_rays_dev entries are live and read; None: rays 0 .. n-1), n_rays_dev int32 on the device (None: all n_rays), n_rays the
+        upper bound (default: len(ray_idx), or R) -> (sample_idx int32 [n_rays*c]: flat indices r*S + s in candidate order, the first
+        counts[0] live; counts int32 [2] = (kept, skipped of the live rays' candidates)), both on the device"""
+        R, S = z.shape
+        dev = z.device
+        self.check_device(dev)
+        if n_rays is None:
+            n_rays = int(ray_idx.shape[0]) if ray_idx is not None else R
+        n_rays, c = int(n_rays), int(c)
+        idx = torch.empty(n_rays * c, device=dev, dtype=torch.int32)
+        counts = torch.zeros(2, device=dev, dtype=torch.int32)
+        L = _lib.lib()
+        ws = torch.empty(int(L.nm_occ_compact_workspace_ints(n_rays * c)), device=dev, dtype=torch.int32)
+        _lib.check(L.nm_occ_compact_ray_chunk(_lib.dev_ptr(self.bits, torch.int32), self.res, self.box_c(), _lib.dev_ptr(o, name='origin'),
+                                              _lib.dev_ptr(d, name='direction'), _lib.dev_ptr(z, name='z_vals'), R, S,
+                                              _lib.dev_ptr(ray_idx, torch.int32, 'ray_idx'), _lib.dev_ptr(n_rays_dev, torch.int32, 'n_rays_dev'), n_rays,
+                                              int(s0), c, _lib.dev_ptr(idx, torch.int32), _lib.dev_ptr(counts, torch.int32), _lib.dev_ptr(ws, torch.int32),
+                                              _lib.stream_ptr()), "nm_occ_compact_ray_chunk")
+        return idx, counts
+
+
 def attach(net, grid):
     """Give `net` (a background Joiner, or a human net: a grid in canonical space) an occupancy grid: its render passes skip the grid's
     empty cells from now on.  Coarse and fine nets have different densities: each gets its own grid (the same object may serve a net used
@@ -228,6 +257,29 @@ def grid_of(net):
     return getattr(net, _ATTR, None) if net is not None else None
 
 
+def forward_listed_samples(net, o, d, z, idx, n_dev, n_max, out, precision=None, role=None, sigma_only=False, chunk_samples=0):
+    """The first *n_dev (int32 on the device; None: n_max) samples listed in idx (flat indices r*S + s; n_max: the list's upper bound) of
+    rays o + d z [R,S] evaluated into the caller's `out` [R,S,4]; nothing else of out is touched.  sigma_only: nm_mlp_sigma_samples;
+    role='composite' where Joiner.live_route says so for n_max samples: nm_mlp_forward_samples_live with the open live workspace
+    (vanilla.live_workspace), in pieces of `chunk_samples`; nm_mlp_forward_samples otherwise."""
+    R, S = z.shape
+    L = _lib.lib()
+    n_max = int(n_max)
+    if net.live_route(precision, role, n_max, sigma_only):
+        from .vanilla import live_workspace_for
+        ws, nbytes = live_workspace_for(n_max, chunk_samples, z.device)
+        _lib.check(L.nm_mlp_forward_samples_live(net.handle(), _lib.dev_ptr(o, name='origin'), _lib.dev_ptr(d, name='direction'), _lib.dev_ptr(z, name='z_vals'),
+                                                 R, S, _lib.dev_ptr(idx, torch.int32), _lib.dev_ptr(n_dev, torch.int32), n_max, net._prec(precision, role), 1.0,
+                                                 _lib.dev_ptr(out), _lib.dev_ptr(ws, torch.uint8), nbytes, int(chunk_samples), _lib.stream_ptr()),
+                   "nm_mlp_forward_samples_live")
+    else:
+        entry = L.nm_mlp_sigma_samples if sigma_only else L.nm_mlp_forward_samples
+        _lib.check(entry(net.handle(), _lib.dev_ptr(o, name='origin'), _lib.dev_ptr(d, name='direction'), _lib.dev_ptr(z, name='z_vals'), R, S,
+                         _lib.dev_ptr(idx, torch.int32), _lib.dev_ptr(n_dev, torch.int32), n_max, net._prec(precision, role), 1.0,
+                         _lib.dev_ptr(out), _lib.stream_ptr()), "nm_mlp_sigma_samples" if sigma_only else "nm_mlp_forward_samples")
+    return out
+
+
 def forward_rays(net, o, d, z, precision=None, role=None, sigma_only=False, stats=None, chunk_samples=0):
     """net.forward_rays over the grid's occupied samples only: raw [R,S,4], zero on every skipped sample.  `stats` (a dict)
     receives 'evaluated' / 'total' sample counts (one host read).  role='composite': as Joiner.forward_rays -- the colour head runs on the
@@ -240,19 +292,7 @@ def forward_rays(net, o, d, z, precision=None, role=None, sigma_only=False, stat
     if R == 0:
         return raw
     idx, counts = grid.compact(o, d, z)
-    L = _lib.lib()
-    if net.live_route(precision, role, R * S, sigma_only):
-        from .vanilla import live_workspace_for
-        ws, nbytes = live_workspace_for(R * S, chunk_samples, z.device)
-        _lib.check(L.nm_mlp_forward_samples_live(net.handle(), _lib.dev_ptr(o, name='origin'), _lib.dev_ptr(d, name='direction'), _lib.dev_ptr(z, name='z_vals'),
-                                                 R, S, _lib.dev_ptr(idx, torch.int32), _lib.dev_ptr(counts, torch.int32), R * S, net._prec(precision, role), 1.0,
-                                                 _lib.dev_ptr(raw), _lib.dev_ptr(ws, torch.uint8), nbytes, int(chunk_samples), _lib.stream_ptr()),
-                   "nm_mlp_forward_samples_live")
-    else:
-        entry = L.nm_mlp_sigma_samples if sigma_only else L.nm_mlp_forward_samples
-        _lib.check(entry(net.handle(), _lib.dev_ptr(o, name='origin'), _lib.dev_ptr(d, name='direction'), _lib.dev_ptr(z, name='z_vals'), R, S,
-                         _lib.dev_ptr(idx, torch.int32), _lib.dev_ptr(counts, torch.int32), R * S, net._prec(precision, role), 1.0,
-                         _lib.dev_ptr(raw), _lib.stream_ptr()), "nm_mlp_sigma_samples" if sigma_only else "nm_mlp_forward_samples")
+    forward_listed_samples(net, o, d, z, idx, counts, R * S, raw, precision=precision, role=role, sigma_only=sigma_only, chunk_samples=chunk_samples)
     if stats is not None:
         stats['evaluated'] = stats.get('evaluated', 0) + int(counts[0].item())
         stats['total'] = stats.get('total', 0) + R * S

@@ -37,6 +37,11 @@ TERMINATION_CHUNK = int(os.environ.get("NEUMAN_TERMINATION_CHUNK", "32"))
 # CDF at float32-rounding level, which the inverse CDF amplifies in near-empty bins: 1.6e-4 on the worst pixel of a frame.)
 TERMINATION_COARSE = float(os.environ.get("NEUMAN_TERMINATION_COARSE", "4e-13"))
 TERMINATION_MIN_CHUNK = 16
+# Early ray termination TOGETHER with an occupancy grid on a background net: the marched passes (march_pass_rays with grid=) evaluate, chunk
+# by chunk, only the occupied samples of the live rays (nm_occ_compact_ray_chunk).  Off: the combination is refused (_occupancy_on), as it
+# has been since grids exist.  Off by default: its frame time has not earned it a default (profiles/march_grid.md), and the rule of
+# profiles/live_heads.md admits a route as a default only on a measured gain.  NEUMAN_MARCH_WITH_GRID=1 turns it on.
+MARCH_WITH_GRID = os.environ.get("NEUMAN_MARCH_WITH_GRID", "0") == "1"
 FUSED_HYBRID_RAYS = int(os.environ.get("NEUMAN_FUSED_HYBRID_RAYS", 1 << 17))
 # The multi-person renderer's batch body as ONE C call (render_multi_rays_fused: nm_render_rays_multi, any number of actors merged and composited
 # by one kernel), in batches of FUSED_MULTI_RAYS rays.  Bit-identical to the step-by-step body and tested.  Off by default: measured on the 1080p
@@ -169,7 +174,7 @@ def merged_intervals(z_lists):
 
 
 def march_pass_rays(net, o, d, z, eps, chunk=None, precision=None, role='shading', stats=None, sigma_only=False, occluder=None,
-                    adaptive=None, dz=None):
+                    adaptive=None, dz=None, grid=None):
     """A pass with early ray termination: the S sorted samples of every ray are evaluated front to back in chunks of `chunk`; after
     each chunk the rays whose transmittance (the running product of raw2outputs' factors, nm_transmittance_chunk) is below `eps`
     leave the list (ballot / prefix-sum compaction on the device, nm_compact_hits) and the next MLP launch covers the compacted live
@@ -189,7 +194,14 @@ def march_pass_rays(net, o, d, z, eps, chunk=None, precision=None, role='shading
     boundary, so near the cut a chunk is half its length of wasted evaluations per ray -- and doubled back otherwise.
     adaptive=False: fixed chunks, no host synchronisation between them (and with eps = 0, bit-identical to the unchunked launch).
 
-    -> raw [R,S,4]; `stats` (a dict) receives the evaluation counts."""
+    grid (an occupancy.OccupancyGrid; None: every sample of the live rays, also for a net that has a grid attached): each chunk lists the
+    occupied samples of the live rays (OccupancyGrid.compact_ray_chunk: the cell test of the whole-pass list, on the device) and evaluates
+    that list (occupancy.forward_listed_samples).  A skipped sample keeps raw = 0: the factor 1 - 0 + 1e-10 of the transmittance, what a
+    sample with relu(sigma) = 0 gets -- cuts, chunk lengths and everything after the evaluation are those of the march whose skipped records
+    were zeroed.  With eps = 0 the result is occupancy.forward_rays'.
+
+    -> raw [R,S,4]; `stats` (a dict) receives the evaluation counts: 'evaluated' (samples the network ran on), 'total', 'launches' and -- with
+    a grid -- 'grid_skipped' (candidates of live rays the grid dropped); accumulated on the device, read once at the end."""
     _lib.require_gpu()
     chunk = chunk or TERMINATION_CHUNK
     adaptive = (eps > 0) if adaptive is None else bool(adaptive)
@@ -201,14 +213,23 @@ def march_pass_rays(net, o, d, z, eps, chunk=None, precision=None, role='shading
     live = torch.arange(R, device=dev, dtype=torch.int32)
     counts = torch.tensor([R, 0], device=dev, dtype=torch.int32)
     ws = torch.empty(int(_lib.lib().nm_compact_workspace_ints(R)), device=dev, dtype=torch.int32)
-    evaluated = torch.zeros(1, device=dev, dtype=torch.int64) if stats is not None else None
+    evaluated = torch.zeros(2, device=dev, dtype=torch.int64) if stats is not None else None     # (network evaluations, dropped by the grid)
     o, d, z = o.contiguous(), d.contiguous(), z.contiguous()
+    if grid is not None:
+        net._guard(o, d, z)
     s0, n_live, launches = 0, R, 0
     while s0 < S:
         c = min(chunk, S - s0)
-        if evaluated is not None:
-            evaluated += counts[0].to(torch.int64) * c
-        net.forward_ray_chunk(o, d, z, live, counts, s0, c, raw, precision=precision, role=role, sigma_only=sigma_only)
+        if grid is None:
+            if evaluated is not None:
+                evaluated[0] += counts[0].to(torch.int64) * c
+            net.forward_ray_chunk(o, d, z, live, counts, s0, c, raw, precision=precision, role=role, sigma_only=sigma_only)
+        else:
+            # the live rays' occupied samples of the chunk only; like forward_ray_chunk, the launch is sized by the list's length R
+            idx, kept = grid.compact_ray_chunk(o, d, z, live, counts, s0, c, n_rays=R)
+            if evaluated is not None:
+                evaluated += kept
+            occupancy.forward_listed_samples(net, o, d, z, idx, kept, R * c, raw, precision=precision, role=role, sigma_only=sigma_only)
         launches += 1
         s0 += c
         if s0 >= S or eps <= 0:                                   # (eps = 0: nothing is ever dropped, not even rays whose T underflowed to 0)
@@ -228,8 +249,10 @@ def march_pass_rays(net, o, d, z, eps, chunk=None, precision=None, role='shading
             chunk = max(TERMINATION_MIN_CHUNK, chunk // 2) if cut > 0.02 else min(max(chunk, TERMINATION_CHUNK), chunk * 2)
             n_live = n_new
     if stats is not None:
-        n = int(evaluated.item())
+        n, skipped = evaluated.tolist()
         stats['evaluated'] = stats.get('evaluated', 0) + n
+        if grid is not None:
+            stats['grid_skipped'] = stats.get('grid_skipped', 0) + skipped
         stats['total'] = stats.get('total', 0) + R * S
         stats['launches'] = stats.get('launches', 0) + launches
     return raw
@@ -349,11 +372,13 @@ def bkg_pass_rays_fused(coarse_net, fine_net, o, d, near, far, samples_per_ray, 
 
 
 def _occupancy_on(*nets):
-    """Does a background pass of these nets skip empty space (occupancy.attach)?  Refuses the combination with early termination."""
+    """Does a background pass of these nets skip empty space (occupancy.attach)?  Refuses the combination with early termination unless
+    MARCH_WITH_GRID (the marched passes then take the grid: bkg_place_z, bkg_shade)."""
     on = any(occupancy.grid_of(n_) is not None for n_ in nets)
-    if on and TERMINATION_EPS > 0:
+    if on and TERMINATION_EPS > 0 and not MARCH_WITH_GRID:
         raise NotImplementedError("an occupancy grid together with early ray termination (TERMINATION_EPS > 0) is not served: "
-                                  "detach the grid or set TERMINATION_EPS = 0")
+                                  "detach the grid or set TERMINATION_EPS = 0 (or take the switched route: NEUMAN_MARCH_WITH_GRID=1, "
+                                  "render_utils.MARCH_WITH_GRID)")
     return on
 
 
@@ -370,11 +395,13 @@ def bkg_place_z(coarse_net, fine_net, o, d, near, far, samples_per_ray, importan
     """Where the background list's FINAL samples are (render_utils.py:131-147, 287-293): the stratified samples, or -- with a fine net --
     the coarse density pass, its compositing weights and the importance samples merged in.  -> (z [R,S'], raw of the coarse pass when it
     is the pass that is composited [no fine net; evaluated here unless termination is on], else None).  composite_only: as bkg_shade, for that
-    raw (the single-net pass, gridded or whole)"""
+    raw (the single-net pass, gridded or whole).  A grid on the coarse net together with TERMINATION_EPS > 0 (MARCH_WITH_GRID, else
+    refused): the coarse pass of a two-net render is marched at TERMINATION_COARSE on its occupied samples (trace key march_coarse); the
+    single-net pass is left to bkg_shade, as without a grid"""
     role = 'composite' if composite_only and LIVE_HEADS else 'shading'
     occ = _occupancy_on(coarse_net)
     _, _, z = ray_utils.sample_z(o, d, near, far, samples_per_ray)
-    if occ:
+    if occ and TERMINATION_EPS <= 0:
         # empty-space skipping (occupancy.py): skipped samples keep raw = 0 -- weight 0, as relu(sigma) = 0 gives
         if fine_net is None:
             return z, _occupancy_pass(coarse_net, o, d, z, precision, role, False, trace, 'occupancy_coarse')
@@ -390,7 +417,8 @@ def bkg_place_z(coarse_net, fine_net, o, d, near, far, samples_per_ray, importan
         # marched at TERMINATION_COARSE on its own transmittance only (where the importance samples go must not depend on what the
         # list is merged with later)
         stats = {} if trace is not None else None
-        raw = march_pass_rays(coarse_net, o, d, z, TERMINATION_COARSE, precision=precision, role=None, stats=stats, sigma_only=True)
+        raw = march_pass_rays(coarse_net, o, d, z, TERMINATION_COARSE, precision=precision, role=None, stats=stats, sigma_only=True,
+                              grid=occupancy.grid_of(coarse_net) if occ else None)
         _note(trace, march_coarse=stats)
     else:
         raw = coarse_net.forward_rays(o, d, z, precision=precision, role=None, sigma_only=True)
@@ -404,13 +432,17 @@ def bkg_shade(net, o, d, z, precision=None, trace=None, occluder=None, dz=None, 
     """The background pass that is composited, on its final samples (render_utils.py:148-151, 294-297): whole, or -- TERMINATION_EPS > 0 --
     marched front to back at eps (`occluder`, `dz`: march_pass_rays), or -- a grid attached (occupancy.attach) -- on its occupied samples.
     composite_only: the caller feeds the raw to raw2outputs and to nothing else, so the whole pass may leave the colour of a sample without
-    density at 0 (Joiner.forward_rays role='composite': its weight is exactly 0); with LIVE_HEADS so may the marched and the gridded pass"""
+    density at 0 (Joiner.forward_rays role='composite': its weight is exactly 0); with LIVE_HEADS so may the marched and the gridded pass.
+    A grid together with TERMINATION_EPS > 0 (MARCH_WITH_GRID, else refused): the marched pass on the occupied samples of its live rays
+    (march_pass_rays grid=; trace key march, with 'grid_skipped')"""
     role = 'composite' if composite_only and LIVE_HEADS else 'shading'
-    if _occupancy_on(net):
+    occ = _occupancy_on(net)
+    if occ and TERMINATION_EPS <= 0:
         return _occupancy_pass(net, o, d, z, precision, role, False, trace, 'occupancy')
     if TERMINATION_EPS > 0:
         stats = {} if trace is not None else None
-        raw = march_pass_rays(net, o, d, z, TERMINATION_EPS, precision=precision, role=role, stats=stats, occluder=occluder, dz=dz)
+        raw = march_pass_rays(net, o, d, z, TERMINATION_EPS, precision=precision, role=role, stats=stats, occluder=occluder, dz=dz,
+                              grid=occupancy.grid_of(net) if occ else None)
         _note(trace, march=stats)
         return raw
     return net.forward_rays(o, d, z, precision=precision, role='composite' if composite_only else 'shading')
@@ -929,7 +961,7 @@ def _render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far
         last_net = fine_bkg if fine_bkg is not None else coarse_bkg
         if last_net._prec(precision, 'shading') == _lib.NM_PREC_I8X3 and (precision or last_net.precision) == 'mixed':
             last = last_net.forward_rays(oc, dc, z_all[:, -1:].contiguous(), precision='fp16x3')[:, 0, :]
-            if TERMINATION_EPS > 0:                                                              # a sample the march never reached stays unevaluated
+            if TERMINATION_EPS > 0:                                                              # a sample the march never reached (or, marched with a grid, that the grid skipped) stays unevaluated
                 last = torch.where((raw_all[:, -1, :] == 0).all(-1, keepdim=True), raw_all[:, -1, :], last)
             raw_all[:, -1, :] = last
         if lists is None and len(human_nets) <= 3 and MULTI_COMPACT:
