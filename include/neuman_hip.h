@@ -390,6 +390,24 @@ int nm_transmittance_chunk(const float* raw, const float* z_vals, const float* r
  * successor in the merged order, and the transmittance the early-termination cut is decided on is the merged list's. */
 int nm_transmittance_chunk_dz(const float* raw, const float* dz, const float* rays_d, const int32_t* ray_idx, const int32_t* n_rays_dev,
                               int64_t n_rays, int s0, int S, int S_total, float* T, nm_stream_t stream);
+/* One marched pass of one net as ONE call (the reference evaluates every sample: utils/render_utils.py:139-151, 294-297): the chunks above,
+ * front to back in uniform chunks of `chunk` samples (the last may be shorter), and between two chunks -- on the device, over the rays of the
+ * live list only, in three launches (transmittance + count, single-block scan, write) -- what a host loop does with nm_transmittance_chunk*
+ * and nm_compact_hits:
+ *   1. T[r] *= prod (1 - alpha_i + 1e-10) over the chunk (render_utils.py:85-95), nm_transmittance_chunk's arithmetic bit for bit; with
+ *      dz [R,S_total] nm_transmittance_chunk_dz's (the samples' intervals in a merged list, :330-345);
+ *   2. with an occluder, T_eff = T[r] * (z_vals[r, s_next] >= occ_z_far[r] ? occ_T[r] : 1), one float32 multiply (s_next: the next chunk's
+ *      first sample): the list will be merged with one that lies in front of occ_z_far and lets occ_T through (:330-345, 441-456);
+ *   3. the ray stays iff eps < T_eff (a NaN drops it); the next list is ascending.
+ * eps <= 0: no boundary runs and every sample is evaluated (the records of nm_mlp_forward_rays / nm_mlp_sigma_rays); none runs after the last
+ * chunk.  raw_out [R,S_total,4] is zeroed here first: a sample never evaluated keeps raw = 0, weight exactly 0 in nm_composite.  sigma_only:
+ * nm_mlp_sigma_ray_chunk instead of nm_mlp_forward_ray_chunk.  stats (nullable, device int64[2]) receives (samples the network ran on, 0).
+ * workspace: workspace_floats >= nm_march_pass_workspace_floats(R) floats, 16-byte aligned like raw_out.  NM_PREC_FP32 has no chunked form.
+ * No host synchronisation, no allocation, no copy to the host; argument errors are reported before anything is enqueued. */
+int64_t nm_march_pass_workspace_floats(int64_t R);
+int nm_march_pass(nm_mlp_t mlp, const float* origin, const float* direction, const float* z_vals, int64_t R, int S_total, int chunk, float eps,
+                  int sigma_only, int precision, float sigma_scale, const float* dz, const float* occ_z_far, const float* occ_T, float* workspace,
+                  int64_t workspace_floats, float* raw_out, int64_t* stats, nm_stream_t stream);
 /* Debug: the density-only NM_PREC_FP16X3 activation-stationary kernel (csrc/mlp_f16t.hip) on n points (out [n,4] = (0, 0, 0, sigma)), plus the
  * activations of its first tile after `stage` (0..7): state [128 samples][256] float32 in natural feature order (hi + lo parts, unscaled). */
 int nm_mlp_sigma_f16t_debug(nm_mlp_t mlp, const float* pts, const float* dirs, int64_t n, int stage, float* state, float* out, nm_stream_t stream);
@@ -521,6 +539,16 @@ int64_t nm_render_rays_bkg_workspace_floats(int64_t R, int S, int N);
 int nm_render_rays_bkg(nm_mlp_t coarse, nm_mlp_t fine, const float* origin, const float* direction, const float* near, const float* far,
                        int64_t R, int S, int N, const float* t_vals, const float* u, int white_bkg, int precision_coarse, int precision_fine,
                        float* workspace, float* raw_out, float* z_out, float* rgb, float* depth, float* acc, nm_stream_t stream);
+/* nm_render_rays_bkg with its passes marched (nm_march_pass above; utils/render_utils.py:131-151 / 287-297 evaluate every sample).  Two nets:
+ * sample -> density-only march of the coarse net at eps_coarse (on its own transmittance: where the importance samples go) ->
+ * nm_importance_from_raw -> march of the fine net at eps -> nm_composite when rgb != NULL.  One net: sample -> march at eps -> composite.
+ * chunk: samples per chunk of both marches.  stats (nullable, device int64[4]): (evaluated, 0) of the composited pass, then of the coarse pass
+ * (zeros with one net).  workspace: workspace_floats >= nm_render_rays_bkg_march_workspace_floats(R, S, N) floats, 16-byte aligned. */
+int64_t nm_render_rays_bkg_march_workspace_floats(int64_t R, int S, int N);
+int nm_render_rays_bkg_march(nm_mlp_t coarse, nm_mlp_t fine, const float* origin, const float* direction, const float* near, const float* far,
+                             int64_t R, int S, int N, const float* t_vals, const float* u, int white_bkg, int precision_coarse, int precision_fine,
+                             float eps, float eps_coarse, int chunk, float* workspace, int64_t workspace_floats, float* raw_out, float* z_out,
+                             float* rgb, float* depth, float* acc, int64_t* stats, nm_stream_t stream);
 int64_t nm_render_rays_human_workspace_floats(int64_t R, int S, int posed);
 int nm_render_rays_human(nm_mlp_t human, nm_mesh_t mesh, const double* T, const float* origin, const float* direction, const float* near,
                          const float* far, int64_t R, int S, const float* t_vals, int white_bkg, float sigma_scale, int precision,

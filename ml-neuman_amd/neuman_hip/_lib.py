@@ -100,6 +100,12 @@ SIGNATURES = {
                                      c_stream]),
     "nm_transmittance_chunk": (i32, [c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, i64, i32, i32, i32, c_f32p, c_stream]),
     "nm_transmittance_chunk_dz": (i32, [c_f32p, c_f32p, c_f32p, c_i32p, c_i32p, i64, i32, i32, i32, c_f32p, c_stream]),
+    "nm_march_pass_workspace_floats": (i64, [i64]),
+    "nm_march_pass": (i32, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, i64, i32, i32, ctypes.c_float, i32, i32, ctypes.c_float, c_f32p, c_f32p, c_f32p, c_f32p,
+                            i64, c_f32p, ctypes.c_void_p, c_stream]),
+    "nm_render_rays_bkg_march_workspace_floats": (i64, [i64, i32, i32]),
+    "nm_render_rays_bkg_march": (i32, [ctypes.c_void_p, ctypes.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, i64, i32, i32, c_f32p, c_f32p, i32, i32, i32,
+                                       ctypes.c_float, ctypes.c_float, i32, c_f32p, i64, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_stream]),
     "nm_mlp_sigma_f16t_debug": (i32, [ctypes.c_void_p, c_f32p, c_f32p, i64, i32, c_f32p, c_f32p, c_stream]),
     "nm_mlp_forward_debug": (i32, [ctypes.c_void_p, c_f32p, c_f32p, i64, i32, i32, c_f32p, c_stream]),
     "nm_mlp_forward_profile": (i32, [ctypes.c_void_p, c_f32p, c_f32p, i64, i32, c_f32p, ctypes.c_void_p, c_stream]),

@@ -42,6 +42,11 @@ TERMINATION_MIN_CHUNK = 16
 # has been since grids exist.  Off by default: its frame time has not earned it a default (profiles/march_grid.md), and the rule of
 # profiles/live_heads.md admits a route as a default only on a measured gain.  NEUMAN_MARCH_WITH_GRID=1 turns it on.
 MARCH_WITH_GRID = os.environ.get("NEUMAN_MARCH_WITH_GRID", "0") == "1"
+# The marched background passes as ONE C call each (march_pass_rays_fused: nm_march_pass -- uniform chunks of TERMINATION_CHUNK samples, the step
+# between two chunks on the device over the live rays only, no host read per chunk).  Taken by bkg_place_z / bkg_shade for a net without a grid,
+# outside the live-heads route; bit-identical to march_pass_rays(adaptive=False).  Off by default: the rule of profiles/live_heads.md admits a
+# route as a default only on a measured gain (profiles/march_fused.md).  NEUMAN_MARCH_FUSED=1 turns it on.
+MARCH_FUSED = os.environ.get("NEUMAN_MARCH_FUSED", "0") == "1"
 FUSED_HYBRID_RAYS = int(os.environ.get("NEUMAN_FUSED_HYBRID_RAYS", 1 << 17))
 # The multi-person renderer's batch body as ONE C call (render_multi_rays_fused: nm_render_rays_multi, any number of actors merged and composited
 # by one kernel), in batches of FUSED_MULTI_RAYS rays.  Bit-identical to the step-by-step body and tested.  Off by default: measured on the 1080p
@@ -258,6 +263,41 @@ def march_pass_rays(net, o, d, z, eps, chunk=None, precision=None, role='shading
     return raw
 
 
+def march_pass_rays_fused(net, o, d, z, eps, chunk=None, precision=None, role='shading', stats=None, sigma_only=False, occluder=None, dz=None):
+    """march_pass_rays(adaptive=False, grid=None) as ONE C call (nm_march_pass): the same chunk launches, and between two of them the
+    transmittance, the occluder's factor, the cut and the compaction on the device over the live rays only (three launches, against a
+    transmittance launch, a handful of ATen ops and a compaction over all R rays) -- the same records, the same counts, bit for bit.  The
+    whole-network chunk launch only: role='composite' runs what 'shading' runs (the live-heads route stays with march_pass_rays).
+    -> raw [R,S,4]; `stats` as march_pass_rays' ('evaluated', 'total', 'launches'), read once at the end."""
+    _lib.require_gpu()
+    chunk = int(chunk or TERMINATION_CHUNK)
+    R, S = z.shape
+    dev = z.device
+    o, d, z = o.contiguous(), d.contiguous(), z.contiguous()
+    net._guard(o, d, z)
+    raw = torch.empty((R, S, 4), device=dev, dtype=torch.float32)
+    n_ws = int(_lib.lib().nm_march_pass_workspace_floats(R))
+    ws = _ws(n_ws, dev)
+    evaluated = torch.empty(2, device=dev, dtype=torch.int64) if stats is not None else None
+    occ_z, occ_T = (None, None) if occluder is None else (occluder[0].to(torch.float32).contiguous(), occluder[1].to(torch.float32).contiguous())
+    _lib.check(_lib.lib().nm_march_pass(
+        net.handle(), _lib.dev_ptr(o, name='origin'), _lib.dev_ptr(d, name='direction'), _lib.dev_ptr(z, name='z_vals'), R, S, chunk, float(eps),
+        int(bool(sigma_only)), net._prec(precision, role), 1.0, _lib.dev_ptr(None if dz is None else dz.contiguous(), name='dz'),
+        _lib.dev_ptr(occ_z, name='occluder z_far'), _lib.dev_ptr(occ_T, name='occluder T'), _lib.dev_ptr(ws), n_ws, _lib.dev_ptr(raw),
+        _lib.dev_ptr(evaluated, torch.int64), _lib.stream_ptr()), "nm_march_pass")
+    if stats is not None:
+        stats['evaluated'] = stats.get('evaluated', 0) + (int(evaluated[0].item()) if R else 0)
+        stats['total'] = stats.get('total', 0) + R * S
+        stats['launches'] = stats.get('launches', 0) + -(-S // chunk)
+    return raw
+
+
+def _march_fused(net, role):
+    """Does a marched background pass of `net` take the one-call route?  MARCH_FUSED, no grid on the net (nm_march_pass evaluates every sample of
+    its live rays) and not the live-heads route (role 'composite' is only ever passed with LIVE_HEADS: nm_mlp_forward_ray_chunk_live)."""
+    return MARCH_FUSED and occupancy.grid_of(net) is None and role != 'composite'
+
+
 def transmittance_of(raw, z, d, dz=None):
     """prod_i (1 - alpha_i + 1e-10) over a whole list: raw2outputs' factors (render_utils.py:85-95) -> T [R].  With the list's own
     intervals (the last one 1e10), or -- `dz`, merged_intervals -- with the intervals it has once merged with other lists."""
@@ -397,7 +437,8 @@ def bkg_place_z(coarse_net, fine_net, o, d, near, far, samples_per_ray, importan
     is the pass that is composited [no fine net; evaluated here unless termination is on], else None).  composite_only: as bkg_shade, for that
     raw (the single-net pass, gridded or whole).  A grid on the coarse net together with TERMINATION_EPS > 0 (MARCH_WITH_GRID, else
     refused): the coarse pass of a two-net render is marched at TERMINATION_COARSE on its occupied samples (trace key march_coarse); the
-    single-net pass is left to bkg_shade, as without a grid"""
+    single-net pass is left to bkg_shade, as without a grid.  MARCH_FUSED: the marched coarse pass of a net without a grid is one C call
+    (march_pass_rays_fused)"""
     role = 'composite' if composite_only and LIVE_HEADS else 'shading'
     occ = _occupancy_on(coarse_net)
     _, _, z = ray_utils.sample_z(o, d, near, far, samples_per_ray)
@@ -417,8 +458,11 @@ def bkg_place_z(coarse_net, fine_net, o, d, near, far, samples_per_ray, importan
         # marched at TERMINATION_COARSE on its own transmittance only (where the importance samples go must not depend on what the
         # list is merged with later)
         stats = {} if trace is not None else None
-        raw = march_pass_rays(coarse_net, o, d, z, TERMINATION_COARSE, precision=precision, role=None, stats=stats, sigma_only=True,
-                              grid=occupancy.grid_of(coarse_net) if occ else None)
+        if _march_fused(coarse_net, None):
+            raw = march_pass_rays_fused(coarse_net, o, d, z, TERMINATION_COARSE, precision=precision, role=None, stats=stats, sigma_only=True)
+        else:
+            raw = march_pass_rays(coarse_net, o, d, z, TERMINATION_COARSE, precision=precision, role=None, stats=stats, sigma_only=True,
+                                  grid=occupancy.grid_of(coarse_net) if occ else None)
         _note(trace, march_coarse=stats)
     else:
         raw = coarse_net.forward_rays(o, d, z, precision=precision, role=None, sigma_only=True)
@@ -434,15 +478,19 @@ def bkg_shade(net, o, d, z, precision=None, trace=None, occluder=None, dz=None, 
     composite_only: the caller feeds the raw to raw2outputs and to nothing else, so the whole pass may leave the colour of a sample without
     density at 0 (Joiner.forward_rays role='composite': its weight is exactly 0); with LIVE_HEADS so may the marched and the gridded pass.
     A grid together with TERMINATION_EPS > 0 (MARCH_WITH_GRID, else refused): the marched pass on the occupied samples of its live rays
-    (march_pass_rays grid=; trace key march, with 'grid_skipped')"""
+    (march_pass_rays grid=; trace key march, with 'grid_skipped').  MARCH_FUSED: the marched pass of a net without a grid, outside the
+    live-heads route, is one C call (march_pass_rays_fused: fixed chunks, no host read between them; same trace keys)"""
     role = 'composite' if composite_only and LIVE_HEADS else 'shading'
     occ = _occupancy_on(net)
     if occ and TERMINATION_EPS <= 0:
         return _occupancy_pass(net, o, d, z, precision, role, False, trace, 'occupancy')
     if TERMINATION_EPS > 0:
         stats = {} if trace is not None else None
-        raw = march_pass_rays(net, o, d, z, TERMINATION_EPS, precision=precision, role=role, stats=stats, occluder=occluder, dz=dz,
-                              grid=occupancy.grid_of(net) if occ else None)
+        if _march_fused(net, role):
+            raw = march_pass_rays_fused(net, o, d, z, TERMINATION_EPS, precision=precision, role=role, stats=stats, occluder=occluder, dz=dz)
+        else:
+            raw = march_pass_rays(net, o, d, z, TERMINATION_EPS, precision=precision, role=role, stats=stats, occluder=occluder, dz=dz,
+                                  grid=occupancy.grid_of(net) if occ else None)
         _note(trace, march=stats)
         return raw
     return net.forward_rays(o, d, z, precision=precision, role='composite' if composite_only else 'shading')
