@@ -610,6 +610,17 @@ int nm_merge_composite_lists(int k, const float* const* z, const float* const* r
  * merged samples per ray (e.g. 320 + 31 x 192 = 6272); more, or k outside 1 .. 32, is refused with NM_ERR_ARG before anything is launched. */
 int nm_merge_composite_lists_wide(int k, const float* const* z, const float* const* raw, const int32_t* const* rows, const int* S, int64_t R,
                                   const float* rays_d, int white_bkg, float* rgb, float* depth, float* acc, nm_stream_t stream);
+/* nm_merge_composite_lists_wide WITH per-list layers (K7d, csrc/merge_layers.hip): the same arguments and contract, the same rgb / depth / acc
+ * bit for bit, and for every list l the sums over ITS samples of what the totals sum over all, with the weight w a sample has in the merged list
+ * (the other lists' occlusion resolved; ties: the earlier list first): layer_acc [R,k] = sum w, layer_rgb [R,k,3] = sum w sigmoid(rgb) --
+ * premultiplied, never with a white background added --, layer_depth [R,k] = sum w z (nullable).  So sum_l layer_rgb_l + white_bkg (1 - sum_l
+ * layer_acc_l) is rgb up to the rounding of the sums.  Deterministic (no atomics); the sums are formed as the totals are, so for k = 1 the layer
+ * equals the totals bit for bit.  At most nm_merge_composite_layers_max_samples(k) merged samples per ray (8014 for every 1 <= k <= 32, 0 for any
+ * other k); more, or k outside 1 .. 32, is refused with NM_ERR_ARG before anything is launched.  No allocation, no synchronisation. */
+int nm_merge_composite_layers_max_samples(int k);
+int nm_merge_composite_layers(int k, const float* const* z, const float* const* raw, const int32_t* const* rows, const int* S, int64_t R,
+                              const float* rays_d, int white_bkg, float* rgb, float* depth, float* acc, float* layer_rgb, float* layer_depth,
+                              float* layer_acc, nm_stream_t stream);
 /* render_hybrid_nerf_multi_persons' per-batch body (utils/render_utils.py:390-456) for A >= 0 actors as one call: two-pass background of
  * every ray (scalar bkg_near / bkg_far, :396-402); when precision_last != 0 the LAST background sample of every ray evaluated once more by
  * the composited net at that NM_PREC_* (nm_mlp_forward_rays on z[:, -1:]; what the host mirror's mixed-precision policy does for the one
@@ -703,6 +714,10 @@ int nm_shot_rays_cams(const int32_t* xy, const int32_t* cam_id, int64_t n, int m
  *   for uint8 inputs.  ssd: device uint64[1].
  * ------------------------------------------------------------------------------------------- */
 int nm_frame_to_uint8(const float* src, int64_t n, uint8_t* dst, nm_stream_t stream);
+/* A premultiplied layer of nm_merge_composite_layers (layer_rgb [n,3], layer_acc [n]) as straight-alpha RGBA bytes [n,4], what a PNG stores:
+ * colour = clamp(rgb / acc, 0, 1) as an f32 quotient, 0 where acc <= 0; alpha = clamp(acc, 0, 1); each channel by nm_frame_to_uint8's rule.
+ * rgba 4-byte aligned. */
+int nm_layers_to_rgba8(const float* layer_rgb, const float* layer_acc, int64_t n, uint8_t* rgba, nm_stream_t stream);
 int nm_ssd_u8(const uint8_t* a, const uint8_t* b, int64_t n, uint64_t* ssd, nm_stream_t stream);
 /* skimage.metrics.structural_similarity(pred, gt, multichannel=True) as render_test_views.py:33 calls it, for uint8 [H,W,C]
  * images: 7x7 uniform window, K1 0.01, K2 0.03, data range 255, sample covariance, mean over the image cropped by 3 pixels

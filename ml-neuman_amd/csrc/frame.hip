@@ -85,12 +85,32 @@ __global__ __launch_bounds__(256) void shot_rays_cams_kernel(const int32_t* __re
 }
 
 // imageio (v2 `image_as_uint`, bitdepth 8) on a float image: clip to [0, 1], then uint8(x * 255 + 0.499999999) in f64
+__device__ __forceinline__ uint8_t to_uint8(float x) {
+    double v = (double)x;
+    v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);                   // NaN falls through both comparisons and converts to 0
+    return (uint8_t)(int)(v * 255.0 + 0.499999999);
+}
 __global__ __launch_bounds__(256) void to_uint8_kernel(const float* __restrict__ src, int64_t n, uint8_t* __restrict__ dst) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    double v = (double)src[i];
-    v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);                   // NaN falls through both comparisons and converts to 0
-    dst[i] = (uint8_t)(int)(v * 255.0 + 0.499999999);
+    dst[i] = to_uint8(src[i]);
+}
+
+// A premultiplied layer (nm_merge_composite_layers: colour sums without a background, and their opacity) as straight-alpha RGBA, what PNG
+// stores: colour = clamp(rgb / acc, 0, 1) as an f32 quotient, 0 where acc <= 0; alpha = clamp(acc, 0, 1); each channel by to_uint8's rule.
+// One thread per pixel, its four bytes as one 32-bit store.
+__global__ __launch_bounds__(256) void layers_to_rgba8_kernel(const float* __restrict__ layer_rgb, const float* __restrict__ layer_acc, int64_t n,
+                                                              uint32_t* __restrict__ rgba) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float a = layer_acc[i];
+    uint32_t px = (uint32_t)to_uint8(a) << 24;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float q = a <= 0.f ? 0.f : layer_rgb[i * 3 + c] / a;
+        px |= (uint32_t)to_uint8(q) << (8 * c);
+    }
+    rgba[i] = px;
 }
 
 // sum of squared differences of two uint8 arrays, exact in integers: per-block partial sums then one atomic each
@@ -186,6 +206,16 @@ int nm_frame_to_uint8(const float* src, int64_t n, uint8_t* dst, nm_stream_t str
     if (n == 0) return NM_OK;
     hipLaunchKernelGGL(to_uint8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nm::as_stream(stream), src, n, dst);
     return nm::check_launch("to_uint8_kernel");
+}
+
+int nm_layers_to_rgba8(const float* layer_rgb, const float* layer_acc, int64_t n, uint8_t* rgba, nm_stream_t stream) {
+    NM_REQUIRE(n >= 0, "nm_layers_to_rgba8: negative n");
+    NM_REQUIRE(n == 0 || (layer_rgb && layer_acc && rgba), "nm_layers_to_rgba8: null pointer");
+    NM_REQUIRE((reinterpret_cast<uintptr_t>(rgba) & 3) == 0, "nm_layers_to_rgba8: rgba must be 4-byte aligned");
+    if (n == 0) return NM_OK;
+    hipLaunchKernelGGL(layers_to_rgba8_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, nm::as_stream(stream), layer_rgb, layer_acc, n,
+                       reinterpret_cast<uint32_t*>(rgba));
+    return nm::check_launch("layers_to_rgba8_kernel");
 }
 
 int nm_ssd_u8(const uint8_t* a, const uint8_t* b, int64_t n, uint64_t* ssd, nm_stream_t stream) {

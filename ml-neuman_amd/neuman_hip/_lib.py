@@ -178,6 +178,9 @@ SIGNATURES = {
                                        ctypes.POINTER(ctypes.c_int), i64, c_f32p, i32, c_f32p, c_f32p, c_f32p, c_stream]),
     "nm_merge_composite_lists_wide": (i32, [i32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                             ctypes.POINTER(ctypes.c_int), i64, c_f32p, i32, c_f32p, c_f32p, c_f32p, c_stream]),
+    "nm_merge_composite_layers_max_samples": (i32, [i32]),
+    "nm_merge_composite_layers": (i32, [i32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
+                                        ctypes.POINTER(ctypes.c_int), i64, c_f32p, i32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "nm_render_rays_multi_workspace_floats": (i64, [i64, i32, i32, i32, i32]),
     "nm_render_rays_multi": (i32, [ctypes.c_void_p, ctypes.c_void_p, i32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p),
                                    ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int), ctypes.c_double, c_f32p, c_f32p,
@@ -197,6 +200,7 @@ SIGNATURES = {
     "nm_loss_shape": (i32, [c_f32p, c_f32p, i64, c_f32p, c_f32p, i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, c_f32p, c_f32p, c_f32p,
                             ctypes.c_void_p, c_f32p, c_stream]),
     "nm_frame_to_uint8": (i32, [c_f32p, i64, ctypes.c_void_p, c_stream]),
+    "nm_layers_to_rgba8": (i32, [c_f32p, c_f32p, i64, ctypes.c_void_p, c_stream]),
     "nm_ssd_u8": (i32, [ctypes.c_void_p, ctypes.c_void_p, i64, ctypes.c_void_p, c_stream]),
 }
 

@@ -656,6 +656,36 @@ def merge_composite_lists_wide(z_lists, raw_lists, rays_d, white_bkg=True, rows=
     return rgb, depth, acc
 
 
+def merge_composite_layers(z_lists, raw_lists, rays_d, white_bkg=True, rows=None):
+    """merge_composite_lists_wide with per-list layers (nm_merge_composite_layers, K7d): same arguments, the same rgb / depth / acc bit for bit, and
+    for every list l the sums over its own samples with the weights they have in the MERGED list: layer_rgb [R,k,3] (premultiplied, no background
+    added), layer_depth [R,k], layer_acc [R,k].  -> (rgb, depth, acc, layer_rgb, layer_depth, layer_acc)"""
+    _lib.require_gpu()
+    k = len(z_lists)
+    R = rays_d.shape[0]
+    dev = rays_d.device
+    if not 1 <= k <= WIDE_MERGE_MAX_LISTS or len(raw_lists) != k:
+        raise _lib.NeumanHipError(f"merge_composite_layers: 1 <= k <= {WIDE_MERGE_MAX_LISTS} lists with their records (k={k})")
+    zs = [z.to(torch.float32).contiguous() for z in z_lists]
+    raws = [r_.to(torch.float32).contiguous() for r_ in raw_lists]
+    rows = [None] * k if rows is None else [None if x is None else x.to(torch.int32).contiguous() for x in rows]
+    for l_ in range(k):
+        if rows[l_] is None and zs[l_].shape[0] != R:
+            raise _lib.NeumanHipError(f"merge_composite_layers: list {l_} has {zs[l_].shape[0]} rows for {R} rays")
+    arr = ctypes.c_void_p * k
+    rgb = torch.empty((R, 3), device=dev, dtype=torch.float32)
+    depth = torch.empty(R, device=dev, dtype=torch.float32)
+    acc = torch.empty(R, device=dev, dtype=torch.float32)
+    layer_rgb = torch.empty((R, k, 3), device=dev, dtype=torch.float32)
+    layer_depth = torch.empty((R, k), device=dev, dtype=torch.float32)
+    layer_acc = torch.empty((R, k), device=dev, dtype=torch.float32)
+    _lib.check(_lib.lib().nm_merge_composite_layers(
+        k, arr(*[z.data_ptr() for z in zs]), arr(*[r_.data_ptr() for r_ in raws]), arr(*[None if x is None else x.data_ptr() for x in rows]),
+        (ctypes.c_int * k)(*[int(z.shape[1]) for z in zs]), R, _lib.dev_ptr(rays_d.contiguous()), int(bool(white_bkg)), _lib.dev_ptr(rgb), _lib.dev_ptr(depth),
+        _lib.dev_ptr(acc), _lib.dev_ptr(layer_rgb), _lib.dev_ptr(layer_depth), _lib.dev_ptr(layer_acc), _lib.stream_ptr()), "nm_merge_composite_layers")
+    return rgb, depth, acc, layer_rgb, layer_depth, layer_acc
+
+
 def render_smpl_nerf_rays(human_net, o, d, posed_verts, mesh, samples_per_ray, white_bkg=True, render_can=False,
                           geo_threshold=DEFAULT_GEO_THRESH, interval_comp=1.0, precision=None, trace=None, given=None):
     """Device core of render_smpl_nerf -> (rgb [R,3], depth [R], acc [R]) CUDA.  `given`: see bkg_pass_rays."""
@@ -711,15 +741,39 @@ def render_hybrid_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far,
                                    white_bkg, geo_threshold, precision, trace, given)
 
 
+def _new_layers(layers, R, L, device):
+    """the per-ray layer arrays of a layered render, zero (an actor a ray misses contributes nothing), into the caller's dict"""
+    layers.update(layer_rgb=torch.zeros((R, L, 3), device=device, dtype=torch.float32), layer_depth=torch.zeros((R, L), device=device, dtype=torch.float32),
+                  layer_acc=torch.zeros((R, L), device=device, dtype=torch.float32))
+    return layers['layer_rgb'], layers['layer_depth'], layers['layer_acc']
+
+
+def render_hybrid_layers_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far, posed_verts, mesh, samples_per_ray,
+                              importance_samples_per_ray, white_bkg=True, geo_threshold=DEFAULT_GEO_THRESH, precision=None, trace=None,
+                              given=None):
+    """render_hybrid_rays with the picture kept in layers: same arguments -> dict of rgb [R,3] and depth [R] (bit-identical to render_hybrid_rays)
+    and layer_rgb [R,2,3], layer_depth [R,2], layer_acc [R,2]: layer 0 the background, layer 1 the actor, each the premultiplied sums of its own
+    samples with the weights they have in the merged list (merge_composite_layers).  A ray that misses the body has the background-only
+    composite in layer 0 and an empty actor layer.  The step-by-step body with its last merge exchanged; never the one-call route."""
+    S_max = int(samples_per_ray) + (int(importance_samples_per_ray) if fine_bkg is not None else 0)
+    layers = {}
+    with raw_composited_only(min(o.shape[0], MAX_RAYS_PER_LAUNCH) * S_max, o.device):
+        rgb, depth, _ = _render_hybrid_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far, posed_verts, mesh, samples_per_ray,
+                                            importance_samples_per_ray, white_bkg, geo_threshold, precision, trace, given, layers=layers)
+    return dict(rgb=rgb, depth=depth, **layers)
+
+
 def _render_hybrid_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far, posed_verts, mesh, samples_per_ray, importance_samples_per_ray, white_bkg,
-                        geo_threshold, precision, trace, given):
-    if TERMINATION_EPS <= 0 and trace is None and given is None and not _occupancy_on(coarse_bkg, fine_bkg) and occupancy.grid_of(human_net) is None:
+                        geo_threshold, precision, trace, given, layers=None):
+    if layers is None and TERMINATION_EPS <= 0 and trace is None and given is None and not _occupancy_on(coarse_bkg, fine_bkg) and occupancy.grid_of(human_net) is None:
         return render_hybrid_rays_fused(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far, posed_verts, mesh, samples_per_ray,
                                         importance_samples_per_ray, white_bkg, geo_threshold, precision)
     R = o.shape[0]
     rgb = torch.empty((R, 3), device=o.device, dtype=torch.float32)
     depth = torch.empty(R, device=o.device, dtype=torch.float32)
     acc = torch.zeros(R, device=o.device, dtype=torch.float32)                                   # misses: acc forced 0, :311
+    if layers is not None:
+        l_rgb, l_depth, l_acc = _new_layers(layers, R, 2, o.device)
     for i, j in _chunks(R):
         oc, dc = o[i:j].contiguous(), d[i:j].contiguous()
         n = torch.full((j - i,), float(bkg_near), device=o.device, dtype=torch.float32)
@@ -771,11 +825,20 @@ def _render_hybrid_rays(coarse_bkg, fine_bkg, human_net, o, d, bkg_near, bkg_far
                                            white_bkg, precision, trace, given_z, composite_only=LIVE_HEADS)
             hit, hd, hf, h_raw, h_z = human_lists()
         # every ray first gets the background-only composite (what the reference does for misses, :303-311) ...
-        rgb[i:j], _, _, _, depth[i:j] = raw2outputs(bkg_raw, bkg_z, dc, white_bkg=white_bkg, want_weights=False)
+        if layers is None:
+            rgb[i:j], _, _, _, depth[i:j] = raw2outputs(bkg_raw, bkg_z, dc, white_bkg=white_bkg, want_weights=False)
+        else:                                                      # (the same composite as a one-list layered merge: its premultiplied sums are layer 0)
+            rgb[i:j], depth[i:j], _, lr, ld, la = merge_composite_layers([bkg_z], [bkg_raw], dc, white_bkg)
+            l_rgb[i:j, 0], l_depth[i:j, 0], l_acc[i:j, 0] = lr[:, 0], ld[:, 0], la[:, 0]
         if hit.numel() == 0:
             continue
         # ... and hit rays are overwritten by the merged human + background composite (:313-353)
-        _rgb, _depth, _ = merge_composite_lists([bkg_z, h_z], [bkg_raw, h_raw], hd, white_bkg, rows=[hit, None])     # (the background rows in place)
+        if layers is None:
+            _rgb, _depth, _ = merge_composite_lists([bkg_z, h_z], [bkg_raw, h_raw], hd, white_bkg, rows=[hit, None])     # (the background rows in place)
+        else:
+            _rgb, _depth, _, lr, ld, la = merge_composite_layers([bkg_z, h_z], [bkg_raw, h_raw], hd, white_bkg, rows=[hit, None])
+            for dst, src in ((l_rgb, lr), (l_depth, ld), (l_acc, la)):
+                ray_utils.scatter_rows(dst[i:j], hit, src)
         _, _, _acc, _, _ = raw2outputs(h_raw, h_z, hd, white_bkg=white_bkg, want_weights=False)          # :345-350
         ray_utils.scatter_rows(rgb[i:j], hit, _rgb)
         ray_utils.scatter_rows(depth[i:j], hit, _depth)
@@ -902,9 +965,24 @@ def render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far,
                                   white_bkg, geo_threshold, precision, trace, given)
 
 
+def render_multi_layers_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far, posed_verts, meshes, samples_per_ray,
+                             importance_samples_per_ray, white_bkg=True, geo_threshold=DEFAULT_GEO_THRESH, precision=None, trace=None,
+                             given=None):
+    """render_multi_rays with the picture kept in layers: same arguments (up to 31 actors) -> dict of rgb [R,3] and depth [R] (bit-identical to
+    render_multi_rays) and layer_rgb [R,L,3], layer_depth [R,L], layer_acc [R,L], L = 1 + actors: layer 0 the background, layer 1 + a actor a in
+    the caller's order, each the premultiplied sums of its own samples with the weights they have in the merged list (merge_composite_layers).
+    The step-by-step body with its last merge exchanged; never the one-call route."""
+    S_max = int(samples_per_ray) + (int(importance_samples_per_ray) if fine_bkg is not None else 0)
+    layers = {}
+    with raw_composited_only(min(o.shape[0], MAX_RAYS_PER_LAUNCH) * S_max, o.device):
+        rgb, depth = _render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far, posed_verts, meshes, samples_per_ray,
+                                        importance_samples_per_ray, white_bkg, geo_threshold, precision, trace, given, layers=layers)
+    return dict(rgb=rgb, depth=depth, **layers)
+
+
 def _render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far, posed_verts, meshes, samples_per_ray, importance_samples_per_ray, white_bkg,
-                       geo_threshold, precision, trace, given):
-    if (MULTI_FUSED and TERMINATION_EPS <= 0 and trace is None and given is None and not _occupancy_on(coarse_bkg, fine_bkg)
+                       geo_threshold, precision, trace, given, layers=None):
+    if (layers is None and MULTI_FUSED and TERMINATION_EPS <= 0 and trace is None and given is None and not _occupancy_on(coarse_bkg, fine_bkg)
             and all(occupancy.grid_of(h_) is None for h_ in human_nets)
             and len({h_._prec(precision, 'shading') for h_ in human_nets}) <= 1                   # (the call takes ONE precision for the actors' nets)
             and multi_merge_stages(len(human_nets), samples_per_ray, importance_samples_per_ray if fine_bkg is not None else 0)):
@@ -913,6 +991,8 @@ def _render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far
     R = o.shape[0]
     rgb = torch.empty((R, 3), device=o.device, dtype=torch.float32)
     depth = torch.empty(R, device=o.device, dtype=torch.float32)
+    if layers is not None:
+        l_rgb, l_depth, l_acc = _new_layers(layers, R, 1 + len(human_nets), o.device)
     for i, j in _chunks(R):
         oc, dc = o[i:j].contiguous(), d[i:j].contiguous()
         nr = j - i
@@ -1012,6 +1092,15 @@ def _render_multi_rays(coarse_bkg, fine_bkg, human_nets, o, d, bkg_near, bkg_far
             if TERMINATION_EPS > 0:                                                              # a sample the march never reached (or, marched with a grid, that the grid skipped) stays unevaluated
                 last = torch.where((raw_all[:, -1, :] == 0).all(-1, keepdim=True), raw_all[:, -1, :], last)
             raw_all[:, -1, :] = last
+        if layers is not None:                                                                   # the same lists, compact or full, through the layered merge
+            if lists is None and MULTI_COMPACT:
+                cl = [actor_lists_compact(a_) for a_ in range(len(human_nets))]
+                zs, raws, rws = [z_all] + [c[0] for c in cl], [raw_all] + [c[1] for c in cl], [None] + [c[2] for c in cl]
+            else:
+                lists = [actor_lists(a_) for a_ in range(len(human_nets))] if lists is None else lists
+                zs, raws, rws = [z_all] + [l_[0] for l_ in lists], [raw_all] + [l_[1] for l_ in lists], None
+            rgb[i:j], depth[i:j], _, l_rgb[i:j], l_depth[i:j], l_acc[i:j] = merge_composite_layers(zs, raws, dc, white_bkg, rows=rws)
+            continue
         if lists is None and len(human_nets) <= 3 and MULTI_COMPACT:
             cl = [actor_lists_compact(a_) for a_ in range(len(human_nets))]
             rgb[i:j], depth[i:j], _ = merge_composite_lists([z_all] + [c[0] for c in cl], [raw_all] + [c[1] for c in cl], dc, white_bkg, rows=[None] + [c[2] for c in cl])
@@ -1223,3 +1312,76 @@ def render_hybrid_nerf_multi_persons(bkg_model, cap, human_models, posed_verts, 
         rgb = rgb.reshape(*cap.shape, -1).cpu().numpy()
         depth = depth.reshape(*cap.shape).cpu().numpy()
     return (rgb, depth) if return_depth else rgb
+
+
+# ------------------------------------------------------------------------------------------------
+# layered frames: the hybrid renderers' picture per source (background, each actor); no counterpart in the reference
+# ------------------------------------------------------------------------------------------------
+_LAYER_KEYS = ('rgb', 'depth', 'layer_rgb', 'layer_depth', 'layer_acc')
+
+
+def _layers_frame(out, cap):
+    """the per-ray tensors of a layered render (in _LAYER_KEYS' order) -> dict of numpy arrays [H,W,...]"""
+    return {k_: x.reshape(*cap.shape, *x.shape[1:]).cpu().numpy() for k_, x in zip(_LAYER_KEYS, out)}
+
+
+def render_hybrid_nerf_layers(net, cap, posed_verts, faces, Ts, rays_per_batch=32768, samples_per_ray=64,
+                              importance_samples_per_ray=128, white_bkg=True, geo_threshold=DEFAULT_GEO_THRESH):
+    """render_hybrid_nerf in layers (render_hybrid_layers_rays): dict of numpy rgb [H,W,3], depth [H,W] -- the frame render_hybrid_nerf returns -- and
+    layer_rgb [H,W,2,3], layer_depth [H,W,2], layer_acc [H,W,2]: layer 0 the background, layer 1 the actor, premultiplied.  None on the ranks
+    other than 0 of a sharded render."""
+    device = _device_of(net)
+    with torch.no_grad():
+        o, d = _pixel_rays(cap, device)
+        verts = torch.as_tensor(np.ascontiguousarray(posed_verts, dtype=np.float32)).to(device)
+        mesh = ray_utils.mesh_to_device(posed_verts, faces, Ts, device)
+
+        def rays_fn(oo, dd):
+            out = render_hybrid_layers_rays(net.coarse_bkg_net, net.fine_bkg_net, net.coarse_human_net, oo, dd, cap.near['bkg'], cap.far['bkg'], verts, mesh,
+                                            samples_per_ray, importance_samples_per_ray, white_bkg, geo_threshold)
+            return tuple(out[k_] for k_ in _LAYER_KEYS)
+        out = _frame(rays_fn, o, d)
+        return None if out is None else _layers_frame(out, cap)
+
+
+def render_hybrid_nerf_multi_persons_layers(bkg_model, cap, human_models, posed_verts, faces, Ts, rays_per_batch=32768, samples_per_ray=64,
+                                            importance_samples_per_ray=128, white_bkg=True, geo_threshold=DEFAULT_GEO_THRESH):
+    """render_hybrid_nerf_multi_persons in layers (render_multi_layers_rays): dict of numpy rgb [H,W,3], depth [H,W] and layer_rgb [H,W,L,3],
+    layer_depth [H,W,L], layer_acc [H,W,L], L = 1 + actors: layer 0 the background, layer 1 + a actor a, premultiplied.  None on the ranks other
+    than 0 of a sharded render."""
+    device = _device_of(bkg_model)
+    with torch.no_grad():
+        o, d = _pixel_rays(cap, device)
+        verts = [torch.as_tensor(np.ascontiguousarray(v, dtype=np.float32)).to(device) for v in posed_verts]
+        meshes = [ray_utils.mesh_to_device(v, f, t, device) for v, f, t in zip(posed_verts, faces, Ts)]
+
+        def rays_fn(oo, dd):
+            out = render_multi_layers_rays(bkg_model.coarse_bkg_net, bkg_model.fine_bkg_net, [m.coarse_human_net for m in human_models], oo, dd,
+                                           cap.near['bkg'], cap.far['bkg'], verts, meshes, samples_per_ray, importance_samples_per_ray, white_bkg, geo_threshold)
+            return tuple(out[k_] for k_ in _LAYER_KEYS)
+        out = _frame(rays_fn, o, d)
+        return None if out is None else _layers_frame(out, cap)
+
+
+def layers_to_rgba_uint8(layer_rgb, layer_acc):
+    """Premultiplied layers [..., 3] and their opacity [...] -> straight-alpha RGBA uint8 [..., 4] on the device (nm_layers_to_rgba8), what save_png
+    writes as a 4-channel PNG: colour clamp(rgb / acc, 0, 1), 0 where acc <= 0; alpha clamp(acc, 0, 1); quantised as frame_to_uint8 does."""
+    _lib.require_gpu()
+    acc = torch.as_tensor(layer_acc).to('cuda', torch.float32).contiguous()
+    rgb = torch.as_tensor(layer_rgb).to(acc.device, torch.float32).contiguous()
+    if rgb.shape != (*acc.shape, 3):
+        raise _lib.NeumanHipError(f"layers_to_rgba_uint8: layer_rgb {tuple(rgb.shape)} is not layer_acc {tuple(acc.shape)} + (3,)")
+    dst = torch.empty((*acc.shape, 4), device=acc.device, dtype=torch.uint8)
+    _lib.check(_lib.lib().nm_layers_to_rgba8(_lib.dev_ptr(rgb), _lib.dev_ptr(acc), acc.numel(), ctypes.c_void_p(dst.data_ptr()), _lib.stream_ptr()),
+               "nm_layers_to_rgba8")
+    return dst
+
+
+def compose_over(layer_rgb, layer_acc, image, layers=None):
+    """The chosen layers over an image: sum_l layer_rgb_l + (1 - sum_l layer_acc_l) image, l in `layers` (default: every actor layer, 1 .. L-1 -- the
+    rendered actors over a photograph instead of over the background NeRF).  layer_rgb [...,L,3], layer_acc [...,L], image [...,3] (or a
+    colour [3]); plain torch on the tensors' device."""
+    layer_rgb, layer_acc = torch.as_tensor(layer_rgb), torch.as_tensor(layer_acc)
+    idx = list(range(1, layer_acc.shape[-1])) if layers is None else [int(l_) for l_ in layers]
+    image = torch.as_tensor(image).to(layer_rgb.device, layer_rgb.dtype)
+    return layer_rgb[..., idx, :].sum(-2) + (1.0 - layer_acc[..., idx].sum(-1))[..., None] * image
