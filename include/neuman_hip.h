@@ -726,6 +726,48 @@ int nm_ssd_u8(const uint8_t* a, const uint8_t* b, int64_t n, uint64_t* ssd, nm_s
 int nm_ssim_u8(const uint8_t* a, const uint8_t* b, int H, int W, int C, double* ssim, double* workspace, nm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * mesh rasteriser -- reference utils/render_utils.py:464-501 (phong_renderer_from_pinhole_cam,
+ *   overlay_smpl) and trainers/human_nerf_trainer.py:478-481 (the SMPL overlay of validate()).
+ *   The reference sits on pytorch3d 0.6.2 (environment.yml, not vendored, absent here):
+ *   RasterizationSettings(blur_radius=0, faces_per_pixel=1), PerspectiveCameras(in_ndc=False),
+ *   HardPhongShader, PointLights(location=(2,2,-2)), white vertices, default Materials / BlendParams;
+ *   with R = R_w2c^T, T = t_w2c, principal point (W - cx, H - cy) and the rot90(k=2) of :497 its
+ *   conventions cancel to the plain pinhole model stated here.  Parity with pytorch3d itself is NOT
+ *   pinned by a golden; tests/helpers/raster_ref.py restates this contract in float64.
+ *     1 projection  Xc = R Xw + t (w2c: HOST f64 [3][4] row-major), u = fx Xc.x / Xc.z + cx, v = fy Xc.y / Xc.z + cy;
+ *                   pixel (row r, column c) is sampled at (c + 0.5, r + 0.5).
+ *     2 coverage    the three screen-space barycentrics of the pixel centre all >= 0 (no top-left rule, no back-face
+ *                   culling); faces of zero screen area are skipped; a face with a vertex at Xc.z <= 0 is dropped
+ *                   WHOLE (a choice of this library: it is not clipped against the near plane).
+ *     3 visibility  b_i' = (b_i / z_i) / sum_j (b_j / z_j), z = 1 / sum_i (b_i / z_i); the nearest z wins, the lower face
+ *                   index on an exact tie -- the result does not depend on binning or scheduling order.
+ *     4 shading     per pixel, world space: vertex normal = normalize(sum over the vertex's faces of cross(v1 - v0, v2 - v0)),
+ *                   n = normalize(sum b_i' n_i), p = sum b_i' v_i, l = normalize(light - p), w = normalize(C - p) with C the
+ *                   camera centre (normalize(x) = x / max(|x|, 1e-6)); colour = 0.5 + 0.3 max(n.l, 0)
+ *                   + 0.2 [n.l > 0] max((2 (n.l) n - l).w, 0)^64 on the three channels, alpha 1; uncovered pixels (1, 1, 1, 0).
+ *     5 overlay     covered pixels take uint8(colour * 255) (truncated, as np.uint8 does at :498), all others keep the image's
+ *                   byte (Image.alpha_composite with alpha in {0, 255} is a select).
+ *   nm_raster_create: faces HOST int32 [F,3] (every index is checked against V before any device work); the handle owns the
+ *     topology, the vertex -> face table of the normals and the scratch of the passes, which grows to the largest image seen.
+ *     Calls on one handle must be issued on one stream at a time.  The tile lists are sized exactly, from a scan of the per-tile
+ *     counts: one 4-byte read-back (a stream synchronise) per call.
+ *   nm_raster_mesh: verts DEVICE f32 [V,3] (world); face_id [H,W] int32, -1 where nothing covers; zbuf [H,W] f32, +inf there;
+ *     bary [H,W,3] f32 (b', zeros there), nullable.
+ *   nm_raster_phong: the same pass plus rule 4: light HOST f64 [3] (world), rgba DEVICE f32 [H,W,4], 16-byte aligned;
+ *     face_id, zbuf and bary are all nullable here.
+ *   nm_overlay_rgba8: rule 5 over n pixels: rgba [n,4] f32 (16-byte aligned), image and out uint8 [n,3] (two buffers).
+ *   NM_ERR_ARG for a null pointer, W * H = 0, F = 0 or an index out of range.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct nm_raster_s* nm_raster_t;
+int nm_raster_create(const int32_t* faces, int F, int V, nm_raster_t* out);
+int nm_raster_destroy(nm_raster_t h);
+int nm_raster_mesh(nm_raster_t h, const float* verts, const double* w2c, double fx, double fy, double cx, double cy, int W, int H,
+                   int32_t* face_id, float* zbuf, float* bary, nm_stream_t stream);
+int nm_raster_phong(nm_raster_t h, const float* verts, const double* w2c, double fx, double fy, double cx, double cy, int W, int H,
+                    int32_t* face_id, float* zbuf, float* bary, const double* light, float* rgba, nm_stream_t stream);
+int nm_overlay_rgba8(const float* rgba, const uint8_t* image, uint8_t* out, int64_t n, nm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SURVEY 8f-1 (first slice): device primitives of a training step of the background NeRF --
  *   reference trainers/vanilla_nerf_trainer.py:45-96 (forward with grad) + torch autograd's backward
  *   of models/vanilla.py:120-152 and utils/render_utils.py:69-105.  The layer loop is host code

@@ -10,7 +10,7 @@ Sub-modules mirror the reference's: ``ray_utils`` (utils/ray_utils.py), ``render
 device); ``parallel`` adds the ray-tile sharding for 1/2/4/8 GPUs; ``synthetic`` the asset-free workloads.  Around the path
 (imported on demand): ``data_io`` + ``scene_content`` (COLMAP / split / checkpoint / per-frame file readers), ``ray_batches``
 (datasets/*.py: training batches drawn on the device), ``train`` + ``bkg_trainer`` + ``human_trainer`` (trainers/*.py),
-``lpips``.  Nothing in this package evaluates the hot path on the CPU.
+``lpips``; ``raster`` (the mesh rasteriser's handle behind ``render_utils.overlay_smpl`` / ``rasterize_mesh`` / ``body_mask``).  Nothing in this package evaluates the hot path on the CPU.
 """
 from . import _lib, parallel, ray_utils, render_utils, smpl, synthetic, vanilla  # noqa: F401
 from ._lib import NeumanHipError  # noqa: F401
@@ -21,7 +21,7 @@ _RAY_FNS = ["shot_ray", "shot_rays", "shot_all_rays", "to_homogeneous", "ray_to_
             "sample_pdf", "geometry_guided_near_far", "geometry_guided_near_far_torch", "geometry_guided_near_far_np",
             "warp_samples_to_canonical", "warp_samples_to_canonical_diff",
             "shot_all_rays_dev", "shot_rays_dev"]                      # additions: a1 on the device (CUDA tensors out)
-_RENDER_FNS = ["raw2outputs", "render_vanilla", "render_smpl_nerf", "render_hybrid_nerf", "render_hybrid_nerf_multi_persons",
+_RENDER_FNS = ["raw2outputs", "render_vanilla", "render_smpl_nerf", "render_hybrid_nerf", "render_hybrid_nerf_multi_persons", "overlay_smpl",
                "frame_to_uint8", "psnr_uint8", "ssim_uint8", "save_png"]                        # additions: the egress of render_test_views.py:83-92, on the device
 _MODEL_CLASSES = ["Embedder", "NeRF", "Joiner", "build_nerf", "OffsetNet", "build_offset_net"]
 

@@ -202,6 +202,13 @@ SIGNATURES = {
     "nm_frame_to_uint8": (i32, [c_f32p, i64, ctypes.c_void_p, c_stream]),
     "nm_layers_to_rgba8": (i32, [c_f32p, c_f32p, i64, ctypes.c_void_p, c_stream]),
     "nm_ssd_u8": (i32, [ctypes.c_void_p, ctypes.c_void_p, i64, ctypes.c_void_p, c_stream]),
+    "nm_raster_create": (i32, [ctypes.c_void_p, i32, i32, ctypes.POINTER(ctypes.c_void_p)]),
+    "nm_raster_destroy": (i32, [ctypes.c_void_p]),
+    "nm_raster_mesh": (i32, [ctypes.c_void_p, c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, i32,
+                             c_i32p, c_f32p, c_f32p, c_stream]),
+    "nm_raster_phong": (i32, [ctypes.c_void_p, c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, i32,
+                              c_i32p, c_f32p, c_f32p, ctypes.POINTER(ctypes.c_double), c_f32p, c_stream]),
+    "nm_overlay_rgba8": (i32, [c_f32p, ctypes.c_void_p, ctypes.c_void_p, i64, c_stream]),
 }
 
 _lib = None

@@ -162,6 +162,20 @@ class HumanNeRFLoss:
         `can_mesh` is either ONE mesh -- a (verts [V,3], faces [F,>=3]) pair -- or PER-FRAME meshes: a dict {cap_id: (verts, faces)}
         or a callable cap_id -> (verts, faces).  (A list / tuple of per-frame pairs is taken as a dict over its indices; anything whose
         first element is not a [V,3] array is rejected rather than guessed at.)  At most `_CAN_TREE_MAX` trees stay on the device."""
+        key, fetch = self._can_mesh_of(cap_id)
+        if key not in self._can_tree:
+            verts, faces = fetch()
+            v = torch.as_tensor(np.ascontiguousarray(verts, dtype=np.float32))
+            if v.ndim != 2 or v.shape[1] != 3:
+                raise ValueError(f"canonical mesh vertices must be [V,3], got {tuple(v.shape)}")
+            while len(self._can_tree) >= self._CAN_TREE_MAX:                             # (oldest first: dicts keep insertion order)
+                self._can_tree.pop(next(iter(self._can_tree)))
+            self._can_tree[key] = ray_utils.Mesh(v, np.ascontiguousarray(np.asarray(faces)[:, :3], np.int32),
+                                                 torch.zeros((v.shape[0], 16), dtype=torch.float64), pts.device)
+        return ray_utils.signed_distance_dev(pts.reshape(-1, 3).detach(), self._can_tree[key])[0]
+
+    def _can_mesh_of(self, cap_id):
+        """-> (key of frame `cap_id`'s canonical mesh: None for the one shared mesh; a call that returns its (verts, faces))"""
         cm = self.can_mesh
         if callable(cm) or isinstance(cm, dict):
             per_frame = True
@@ -174,16 +188,7 @@ class HumanNeRFLoss:
         if per_frame and cap_id is None:
             raise ValueError("per-frame canonical meshes need the batch's cap_id")
         key = int(cap_id) if per_frame else None
-        if key not in self._can_tree:
-            verts, faces = (cm(key) if callable(cm) else cm[key]) if per_frame else cm
-            v = torch.as_tensor(np.ascontiguousarray(verts, dtype=np.float32))
-            if v.ndim != 2 or v.shape[1] != 3:
-                raise ValueError(f"canonical mesh vertices must be [V,3], got {tuple(v.shape)}")
-            while len(self._can_tree) >= self._CAN_TREE_MAX:                             # (oldest first: dicts keep insertion order)
-                self._can_tree.pop(next(iter(self._can_tree)))
-            self._can_tree[key] = ray_utils.Mesh(v, np.ascontiguousarray(np.asarray(faces)[:, :3], np.int32),
-                                                 torch.zeros((v.shape[0], 16), dtype=torch.float64), pts.device)
-        return ray_utils.signed_distance_dev(pts.reshape(-1, 3).detach(), self._can_tree[key])[0]
+        return key, lambda: (cm(key) if callable(cm) else cm[key]) if per_frame else cm
 
     _CAN_TREE_MAX = 8
     _mirror = None
@@ -500,6 +505,24 @@ class HumanNeRFTrainer(HumanNeRFLoss):
             for m in self._modules():
                 m.train()
         return {k: sum(r[k] for r in reports) / len(reports) for k in reports[0]}
+
+    def validation_images(self, cap, image, cap_id, can_cap=None):
+        """The visuals of the reference's validate() (:475-513), opt-in: the canonical render of `can_cap` (default: the first canonical
+        camera) as colour, depth clamped to the opaque pixels' range, and alpha, and the posed body of frame `cap_id` overlaid on `image`
+        (uint8 [H,W,3]) as `cap` sees it -- the picture that shows whether pose optimisation keeps the body on the person.
+        -> [rgb, depth, acc, overlay], each [H,W,3] (float32 x 3, uint8); the reference stacks them, which needs cap and can_cap of one size."""
+        with torch.no_grad():
+            verts, _ = self.net.vertex_forward(int(cap_id))
+            overlay = render_utils.overlay_smpl(image, verts[0], self.faces, cap)
+        can_cap = self.can_caps[0] if can_cap is None else can_cap
+        can_mesh = self._can_mesh_of(cap_id)[1]()
+        rgb_map, depth_map, acc_map = render_utils.render_smpl_nerf(self.net, can_cap, np.asarray(can_mesh[0]), can_mesh[1], None, samples_per_ray=self.opt.samples_per_ray,
+                                                                    white_bkg=True, render_can=True, return_mask=True, return_depth=True,
+                                                                    interval_comp=self.interval_comp)
+        alpha_mask = acc_map >= 0.9999999999
+        if alpha_mask.any():                                                             # (the reference's try / except: no opaque pixel, no clamp)
+            depth_map = np.clip(depth_map, depth_map[alpha_mask].min(), depth_map[alpha_mask].max())
+        return [rgb_map, np.stack([depth_map] * 3, -1), np.stack([acc_map] * 3, -1), overlay]
 
     def train(self, max_iter=None, on_step=None):
         max_iter = self.opt.max_iter if max_iter is None else max_iter

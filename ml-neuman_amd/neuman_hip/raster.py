@@ -1,0 +1,122 @@
+"""The mesh rasteriser's handle (csrc/raster.hip, include/neuman_hip.h 'mesh rasteriser'): one `Rasterizer` per topology holds the
+faces, the vertex -> face table of the normals and the passes' scratch on the device; `rasterizer_for(faces, V)` keeps the last few.
+
+The camera of a capture is read here too: intrinsics from `cap.pinhole_cam` (the reference's captures) or `cap.intrinsic_matrix`
+(synthetic.SimpleCapture), the world-to-camera matrix from `cap.cam_pose` in float64."""
+import collections
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+
+LIGHT = (2.0, 2.0, -2.0)                                           # PointLights(location=...) of render_utils.py:469
+
+
+def camera_of(cap):
+    """(w2c f64 [3,4], fx, fy, cx, cy, W, H) of a capture."""
+    cam = getattr(cap, 'pinhole_cam', None)
+    if cam is not None:
+        fx, fy, cx, cy, W, H = cam.fx, cam.fy, cam.cx, cam.cy, cam.width, cam.height
+    else:
+        K = np.asarray(cap.intrinsic_matrix, np.float64)
+        fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
+        H, W = cap.shape
+    pose = cap.cam_pose
+    if hasattr(pose, 'rotation_matrix') and hasattr(pose, 'translation_vector'):
+        w2c = np.concatenate([np.asarray(pose.rotation_matrix, np.float64)[:3, :3], np.asarray(pose.translation_vector, np.float64).reshape(3, 1)], 1)
+    else:
+        w2c = np.linalg.inv(np.asarray(pose.camera_to_world, np.float64))[:3, :4]
+    return np.ascontiguousarray(w2c), float(fx), float(fy), float(cx), float(cy), int(W), int(H)
+
+
+def _f64(a):
+    a = np.ascontiguousarray(a, np.float64)
+    return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+
+class Rasterizer:
+    """nm_raster_create over faces [F,3] (numpy or tensor, any integer type) of a mesh with V vertices."""
+
+    def __init__(self, faces, V):
+        if isinstance(faces, torch.Tensor):
+            faces = faces.detach().cpu().numpy()
+        self.faces = np.ascontiguousarray(np.asarray(faces)[:, :3], np.int32)
+        self.F, self.V = int(self.faces.shape[0]), int(V)
+        h = ctypes.c_void_p()
+        _lib.check(_lib.lib().nm_raster_create(self.faces.ctypes.data_as(ctypes.c_void_p), self.F, self.V, ctypes.byref(h)), "nm_raster_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, '_h', None):
+            _lib.lib().nm_raster_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _verts(self, verts):
+        if not isinstance(verts, torch.Tensor) or not verts.is_cuda:
+            raise _lib.NeumanHipError("verts must be a CUDA (HIP) tensor: the rasteriser has no CPU path")
+        verts = verts.detach().to(torch.float32).contiguous()
+        if verts.shape != (self.V, 3):
+            raise _lib.NeumanHipError(f"verts {tuple(verts.shape)} is not [{self.V}, 3]")
+        return verts
+
+    def rasterize(self, verts, camera, want_bary=True, shade=False, light=LIGHT):
+        """-> (face_id [H,W] int32, zbuf [H,W] f32, bary [H,W,3] f32 or None, rgba [H,W,4] f32 or None) on verts' device."""
+        verts = self._verts(verts)
+        w2c, fx, fy, cx, cy, W, H = camera
+        if W < 1 or H < 1:
+            raise _lib.NeumanHipError(f"rasterize: empty image {W} x {H}")
+        dev = verts.device
+        with torch.cuda.device(dev):
+            face_id = torch.empty((H, W), device=dev, dtype=torch.int32)
+            zbuf = torch.empty((H, W), device=dev, dtype=torch.float32)
+            bary = torch.empty((H, W, 3), device=dev, dtype=torch.float32) if want_bary else None
+            w2c, w2c_p = _f64(w2c)
+            if shade:
+                rgba = torch.empty((H, W, 4), device=dev, dtype=torch.float32)
+                light, light_p = _f64(light)
+                _lib.check(_lib.lib().nm_raster_phong(self._h, _lib.dev_ptr(verts), w2c_p, fx, fy, cx, cy, W, H, _lib.dev_ptr(face_id, torch.int32),
+                                                      _lib.dev_ptr(zbuf), _lib.dev_ptr(bary), light_p, _lib.dev_ptr(rgba), _lib.stream_ptr()), "nm_raster_phong")
+            else:
+                rgba = None
+                _lib.check(_lib.lib().nm_raster_mesh(self._h, _lib.dev_ptr(verts), w2c_p, fx, fy, cx, cy, W, H, _lib.dev_ptr(face_id, torch.int32),
+                                                     _lib.dev_ptr(zbuf), _lib.dev_ptr(bary), _lib.stream_ptr()), "nm_raster_mesh")
+        return face_id, zbuf, bary, rgba
+
+
+_CACHE = collections.OrderedDict()
+_CACHE_SIZE = 4
+
+
+def rasterizer_for(faces, V):
+    """The handle of this topology, built on first use (a trainer overlays the same body every validation)."""
+    if isinstance(faces, torch.Tensor):
+        faces = faces.detach().cpu().numpy()
+    faces = np.ascontiguousarray(np.asarray(faces)[:, :3], np.int32)
+    key = (int(V), faces.shape[0], hash(faces.tobytes()))
+    r = _CACHE.get(key)
+    if r is None or not np.array_equal(r.faces, faces):
+        r = _CACHE[key] = Rasterizer(faces, V)
+        while len(_CACHE) > _CACHE_SIZE:
+            _CACHE.popitem(last=False)[1].close()
+    _CACHE.move_to_end(key)
+    return r
+
+
+def overlay_rgba(rgba, image):
+    """Rule 5: rgba [H,W,4] f32 (device) over image [H,W,3] uint8 (device) -> uint8 [H,W,3] (device)."""
+    if image.dtype != torch.uint8 or image.shape != (*rgba.shape[:2], 3):
+        raise _lib.NeumanHipError(f"overlay: the image must be uint8 [{rgba.shape[0]}, {rgba.shape[1]}, 3], got {image.dtype} {tuple(image.shape)}")
+    image = image.contiguous()
+    out = torch.empty_like(image)
+    with torch.cuda.device(rgba.device):
+        _lib.check(_lib.lib().nm_overlay_rgba8(_lib.dev_ptr(rgba), _lib.dev_ptr(image, torch.uint8), _lib.dev_ptr(out, torch.uint8), rgba.shape[0] * rgba.shape[1],
+                                               _lib.stream_ptr()), "nm_overlay_rgba8")
+    return out

@@ -1385,3 +1385,39 @@ def compose_over(layer_rgb, layer_acc, image, layers=None):
     idx = list(range(1, layer_acc.shape[-1])) if layers is None else [int(l_) for l_ in layers]
     image = torch.as_tensor(image).to(layer_rgb.device, layer_rgb.dtype)
     return layer_rgb[..., idx, :].sum(-2) + (1.0 - layer_acc[..., idx].sum(-1))[..., None] * image
+
+
+# ------------------------------------------------------------------------------------------------
+# the body as a rasterised mesh (reference render_utils.py:464-501; csrc/raster.hip, the contract in include/neuman_hip.h)
+# ------------------------------------------------------------------------------------------------
+def _raster_of(verts, faces, cap, **kw):
+    from . import raster
+    if not isinstance(verts, torch.Tensor) or not verts.is_cuda:
+        raise _lib.NeumanHipError("verts must be a CUDA (HIP) tensor: the rasteriser has no CPU path")
+    _lib.require_gpu()
+    return raster.rasterizer_for(faces, verts.shape[0]).rasterize(verts, raster.camera_of(cap), **kw)
+
+
+def rasterize_mesh(verts, faces, cap):
+    """The mesh as `cap` sees it -> (face_id [H,W] int32, -1 where nothing covers the pixel centre; zbuf [H,W] f32 camera depth, +inf there;
+    bary [H,W,3] f32 perspective-correct barycentrics of the winning face), device tensors.  verts [V,3] CUDA f32, faces [F,3]."""
+    with torch.no_grad():
+        return _raster_of(verts, faces, cap)[:3]
+
+
+def body_mask(verts, faces, cap):
+    """bool [H,W] on the device: the pixels whose centre the mesh covers."""
+    with torch.no_grad():
+        return _raster_of(verts, faces, cap, want_bary=False)[0] >= 0
+
+
+def overlay_smpl(img, verts, faces, cap):
+    """reference render_utils.py:485-501: the Phong-shaded white body over `img` (uint8 [H,W,3] numpy) -> uint8 [H,W,3] numpy.  Pixels the body
+    does not cover keep img's bytes."""
+    from . import raster
+    with torch.no_grad():
+        rgba = _raster_of(verts, faces, cap, want_bary=False, shade=True)[3]
+        image = torch.as_tensor(np.ascontiguousarray(img))
+        if image.dtype != torch.uint8:
+            raise _lib.NeumanHipError(f"overlay_smpl: img must be uint8, got {image.dtype}")
+        return raster.overlay_rgba(rgba, image[..., :3].contiguous().to(rgba.device)).cpu().numpy()
