@@ -768,6 +768,47 @@ int nm_raster_phong(nm_raster_t h, const float* verts, const double* w2c, double
 int nm_overlay_rgba8(const float* rgba, const uint8_t* image, uint8_t* out, int64_t n, nm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * soft silhouette -- reference preprocess/optimize_smpl.py:84-102 (silhouette_renderer_from_pinhole_cam:
+ *   MeshRasterizer(blur_radius = log(1/1e-4 - 1) sigma, faces_per_pixel = 100) under
+ *   SoftSilhouetteShader(BlendParams(sigma = 1e-4))) and :249-252 (the silhouette term of optimize_smpl
+ *   and its backward to the vertices).  pytorch3d is absent, so parity with it is NOT pinned by a golden,
+ *   as for the rasteriser; tests/helpers/silhouette_ref.py restates this contract in float64.  The
+ *   reference's principal point (W - cx, H - cy) and its rot90(k=2) of :250 cancel to the plain pinhole
+ *   image, as they do for the overlay.  The rasteriser's rules 1 and 2 hold unchanged (float64 pinhole
+ *   projection, pixel centres at (c + 0.5, r + 0.5), a face with a vertex at z <= 0 or of zero screen
+ *   area dropped whole); on top of them:
+ *     S1 distance    for pixel centre c and face k, m_k = the smallest of the squared distances from c to the three edge
+ *                    segments (foot parameter t = clamp(dot(c - a, b - a) / |b - a|^2, 0, 1)), in NDC units:
+ *                    m_k = m_pixels (2 / min(W, H))^2 (pytorch3d maps the shorter image side to [-1, 1]); inside_k is
+ *                    rule 2's coverage test; d_k = -m_k if inside_k, else +m_k.
+ *     S2 candidates  face k contributes to the pixel iff inside_k or m_k < blur_radius (strict).
+ *     S3 blend       q_k = 1 / (1 + exp(-d_k / sigma)) (= 1 - p_k, evaluated directly); keep = prod_k q_k over the
+ *                    candidates; alpha = 1 - keep; a pixel without candidates has keep 1, alpha 0.
+ *     S4 no K cap    EVERY candidate counts.  pytorch3d keeps the faces_per_pixel = 100 nearest in depth; this library
+ *                    does not, and the two coincide wherever a pixel has <= 100 candidates: n_cand [H,W] int32
+ *                    (nullable) returns the count per pixel so that a caller can tell.  Depth plays no other role.
+ *     S5 gradient    the candidate set and inside_k are constants; d alpha / d d_k = -(1 - q_k) keep / sigma;
+ *                    d d_k / d(screen vertices) is that of the winning segment's squared distance (at a clamped foot it
+ *                    goes to that endpoint only), chained through rule 1 to the world-space vertices in float64.
+ *                    keep is SAVED by the forward and read by the backward, never recomputed as 1 - alpha.
+ *     S6 same bits   alpha, keep and g_verts are the same bits on every run: no float atomics; the product of S3 runs in
+ *                    ascending face id, the sums of S5 in a fixed order.
+ *   nm_raster_silhouette: verts DEVICE f32 [V,3] (world); alpha, keep DEVICE f32 [H,W]; n_cand DEVICE int32 [H,W] or null.
+ *     One 4-byte read-back per call, as nm_raster_mesh.  It shares the handle's scratch with the rasteriser: calls on one
+ *     handle go on one stream at a time.
+ *   nm_raster_silhouette_backward: recomputes S1-S2 from verts (the same verts, camera, sigma and blur_radius as the
+ *     forward); keep DEVICE f32 [H,W] from the forward, g_alpha DEVICE f32 [H,W] = d loss / d alpha, g_verts DEVICE f32
+ *     [V,3] (written, not accumulated).  No read-back.
+ *   NM_ERR_ARG (with the entry's name in nm_last_error()) for a null pointer, W * H = 0, NaN intrinsics, sigma not finite
+ *   or <= 0, blur_radius not finite or < 0 -- all checked before any device work.
+ * ------------------------------------------------------------------------------------------- */
+int nm_raster_silhouette(nm_raster_t h, const float* verts, const double* w2c, double fx, double fy, double cx, double cy, int W, int H,
+                         double sigma, double blur_radius, float* alpha, float* keep, int32_t* n_cand, nm_stream_t stream);
+int nm_raster_silhouette_backward(nm_raster_t h, const float* verts, const double* w2c, double fx, double fy, double cx, double cy, int W,
+                                  int H, double sigma, double blur_radius, const float* keep, const float* g_alpha, float* g_verts,
+                                  nm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SURVEY 8f-1 (first slice): device primitives of a training step of the background NeRF --
  *   reference trainers/vanilla_nerf_trainer.py:45-96 (forward with grad) + torch autograd's backward
  *   of models/vanilla.py:120-152 and utils/render_utils.py:69-105.  The layer loop is host code

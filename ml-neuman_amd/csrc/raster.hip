@@ -15,58 +15,19 @@
 // The order inside a tile's list is whatever the atomics made it; the minimum over (z, face id) does not depend on it.  The edge functions are
 // evaluated on vertices translated by the pixel centre (products of differences, no fmaf: cross(b, c) = -cross(c, b) exactly, so the two faces
 // of a shared edge never both reject a pixel), which keeps sub-pixel triangles well conditioned.
-#include "common.h"
+#include "raster_device.h"
 
-#include <math.h>
 #include <string.h>
 
 #include <vector>
 
 namespace {
 
-constexpr int kTile = 16;                    // pixels per tile side; kTile * kTile lanes per workgroup
-constexpr int kBatch = kTile * kTile;        // faces staged through LDS at a time
-constexpr float kNormEps = 1e-6f;            // torch.nn.functional.normalize's eps as pytorch3d calls it: x / max(|x|, eps)
-
-struct Cam {
-    double w2c[12];                          // row-major [3][4]
-    double fx, fy, cx, cy;
-};
+using namespace nm_rast;                     // the handle, the camera, the vertex pass, the scan and the edge functions: raster_device.h
 
 struct Shade {
     float light[3], centre[3];               // world space
 };
-
-// ---- vertex pass ----------------------------------------------------------------------------------------------------------------------
-__global__ void raster_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces, const int32_t* __restrict__ adj_off,
-                                     const int32_t* __restrict__ adj, int V, Cam cam, int want_normals, float4* __restrict__ vscr,
-                                     float* __restrict__ vnrm) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= V) return;
-    const double x = verts[3 * v], y = verts[3 * v + 1], z = verts[3 * v + 2];
-    const double xc = ((cam.w2c[0] * x + cam.w2c[1] * y) + cam.w2c[2] * z) + cam.w2c[3];
-    const double yc = ((cam.w2c[4] * x + cam.w2c[5] * y) + cam.w2c[6] * z) + cam.w2c[7];
-    const double zc = ((cam.w2c[8] * x + cam.w2c[9] * y) + cam.w2c[10] * z) + cam.w2c[11];
-    // a vertex at or behind the camera plane drops its faces whole (face setup reads the sign of .w); its screen position is never used
-    const bool front = zc > 0.0;
-    const double iz = front ? 1.0 / zc : 0.0;
-    vscr[v] = make_float4(front ? (float)(cam.fx * xc * iz + cam.cx) : 0.f, front ? (float)(cam.fy * yc * iz + cam.cy) : 0.f, (float)iz, (float)zc);
-    if (!want_normals) return;
-    double nx = 0.0, ny = 0.0, nz = 0.0;
-    for (int k = adj_off[v]; k < adj_off[v + 1]; ++k) {
-        const int f = adj[k];
-        const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
-        const double ax = (double)verts[3 * i1] - verts[3 * i0], ay = (double)verts[3 * i1 + 1] - verts[3 * i0 + 1], az = (double)verts[3 * i1 + 2] - verts[3 * i0 + 2];
-        const double bx = (double)verts[3 * i2] - verts[3 * i0], by = (double)verts[3 * i2 + 1] - verts[3 * i0 + 1], bz = (double)verts[3 * i2 + 2] - verts[3 * i0 + 2];
-        nx += ay * bz - az * by;
-        ny += az * bx - ax * bz;
-        nz += ax * by - ay * bx;
-    }
-    const double len = fmax(sqrt((nx * nx + ny * ny) + nz * nz), (double)kNormEps);
-    vnrm[3 * v] = (float)(nx / len);
-    vnrm[3 * v + 1] = (float)(ny / len);
-    vnrm[3 * v + 2] = (float)(nz / len);
-}
 
 // ---- face setup and binning -----------------------------------------------------------------------------------------------------------
 // rec[f] = three float4: (x0, y0, x1, y1), (x2, y2, 1/z0, 1/z1), (1/z2, -, -, -); box[f] = tiles (tx0, ty0, tx1, ty1), tx0 > tx1 for a rejected face
@@ -97,24 +58,6 @@ __global__ void raster_face_kernel(const float4* __restrict__ vscr, const int32_
         for (int tx = bx.x; tx <= bx.z; ++tx) atomicAdd(&count[ty * TX + tx], 1);
 }
 
-// exclusive scan of the T tile counts by one workgroup: offset[0 .. T], offset[T] the total; cursor = offset[0 .. T-1] for the fill
-__global__ void raster_scan_kernel(const int32_t* __restrict__ count, int T, int32_t* __restrict__ offset, int32_t* __restrict__ cursor) {
-    __shared__ int part[256];
-    const int per = (T + 255) / 256, lo = threadIdx.x * per, hi = min(lo + per, T);
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += count[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int i = 0; i < 256; ++i) { const int t = part[i]; part[i] = run; run += t; }
-        offset[T] = run;
-    }
-    __syncthreads();
-    int run = part[threadIdx.x];
-    for (int i = lo; i < hi; ++i) { offset[i] = run; cursor[i] = run; run += count[i]; }
-}
-
 __global__ void raster_fill_kernel(const int4* __restrict__ box, int F, int TX, int32_t* __restrict__ cursor, int32_t* __restrict__ list, int cap) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
@@ -127,14 +70,6 @@ __global__ void raster_fill_kernel(const int4* __restrict__ box, int F, int TX, 
 }
 
 // ---- raster and shade -----------------------------------------------------------------------------------------------------------------
-// the three edge functions of the pixel centre, on vertices translated by it: w0 pairs (v1, v2), w1 (v2, v0), w2 (v0, v1)
-__device__ __forceinline__ void edge_functions(const float4 r0, const float4 r1, float px, float py, float& w0, float& w1, float& w2) {
-    const float ax = r0.x - px, ay = r0.y - py, bx = r0.z - px, by = r0.w - py, cx = r1.x - px, cy = r1.y - py;
-    w0 = bx * cy - by * cx;
-    w1 = cx * ay - cy * ax;
-    w2 = ax * by - ay * bx;
-}
-
 __device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
     const float len = fmaxf(sqrtf((x * x + y * y) + z * z), kNormEps);
     x /= len; y /= len; z /= len;
@@ -230,37 +165,15 @@ __global__ void overlay_rgba8_kernel(const float4* __restrict__ rgba, const uint
 
 }  // namespace
 
-struct nm_raster_s {
-    int F, V;
-    int32_t* d_faces;        // [F,3]
-    int32_t* d_adj_off;      // [V+1] vertex -> faces, CSR, ascending face id inside a vertex
-    int32_t* d_adj;          // [3F]
-    float4* d_vscr;          // [V] (u, v, 1/z, z)
-    float* d_vnrm;           // [V,3]
-    float4* d_rec;           // [F][3]
-    int4* d_box;             // [F]
-    int32_t* d_tiles;        // count [T], offset [T+1], cursor [T]: grown to the largest image seen
-    int tiles_cap;
-    int32_t* d_list;         // the tiles' face lists, end to end: grown to the largest total seen
-    int64_t list_cap;
-};
-
 namespace {
 
 int raster_run(const char* who, nm_raster_s* h, const float* verts, const double* w2c, double fx, double fy, double cx, double cy, int W, int H,
                int32_t* face_id, float* zbuf, float* bary, const double* light, float4* rgba, hipStream_t st) {
     const int TX = (W + kTile - 1) / kTile, TY = (H + kTile - 1) / kTile, T = TX * TY;
     int rc = NM_OK;
-    if (T > h->tiles_cap) {
-        if (h->d_tiles) (void)hipFree(h->d_tiles);
-        h->d_tiles = nullptr; h->tiles_cap = 0;
-        if ((rc = nm::check_hip(hipMalloc(&h->d_tiles, (size_t)(3 * T + 1) * 4), "raster: hipMalloc(tiles)"))) return rc;
-        h->tiles_cap = T;
-    }
+    if ((rc = reserve_tiles(h, T))) return rc;
     int32_t *count = h->d_tiles, *offset = count + T, *cursor = offset + T + 1;
-    Cam cam;
-    for (int i = 0; i < 12; ++i) cam.w2c[i] = w2c[i];
-    cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy;
+    const Cam cam = make_cam(w2c, fx, fy, cx, cy);
     Shade sh = {};
     if (rgba) {
         for (int k = 0; k < 3; ++k) {
@@ -279,12 +192,7 @@ int raster_run(const char* who, nm_raster_s* h, const float* verts, const double
     if ((rc = nm::check_hip(hipMemcpyAsync(&total, offset + T, 4, hipMemcpyDeviceToHost, st), "raster: read total"))) return rc;
     if ((rc = nm::check_hip(hipStreamSynchronize(st), "raster: sync"))) return rc;
     if (total < 0) { nm::set_error("%s: the tile lists overflow 2^31 entries", who); return NM_ERR_UNSUPPORTED; }
-    if (total > h->list_cap) {
-        if (h->d_list) (void)hipFree(h->d_list);
-        h->d_list = nullptr; h->list_cap = 0;
-        if ((rc = nm::check_hip(hipMalloc(&h->d_list, (size_t)total * 4), "raster: hipMalloc(lists)"))) return rc;
-        h->list_cap = total;
-    }
+    if ((rc = reserve_lists(h, total))) return rc;
     if (total > 0) hipLaunchKernelGGL(raster_fill_kernel, dim3((h->F + 255) / 256), dim3(256), 0, st, h->d_box, h->F, TX, cursor, h->d_list, total);
     hipLaunchKernelGGL(raster_tile_kernel, dim3(T), dim3(kBatch), 0, st, h->d_rec, offset, h->d_list, h->d_faces, verts, h->d_vnrm, W, H, TX, sh, face_id, zbuf,
                        bary, rgba);
@@ -297,7 +205,7 @@ extern "C" {
 
 int nm_raster_destroy(nm_raster_t h) {
     if (!h) return NM_OK;
-    void* bufs[] = {h->d_faces, h->d_adj_off, h->d_adj, h->d_vscr, h->d_vnrm, h->d_rec, h->d_box, h->d_tiles, h->d_list};
+    void* bufs[] = {h->d_faces, h->d_adj_off, h->d_adj, h->d_vscr, h->d_vnrm, h->d_rec, h->d_box, h->d_tiles, h->d_list, h->d_gface};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete h;
@@ -338,11 +246,6 @@ int nm_raster_create(const int32_t* faces, int F, int V, nm_raster_t* out) {
     *out = h;
     return NM_OK;
 }
-
-#define NM_RASTER_ARGS(who)                                                                                                         \
-    NM_REQUIRE(h && verts && w2c, who ": null pointer");                                                                            \
-    NM_REQUIRE(W >= 1 && H >= 1 && (int64_t)W * H <= (1ll << 30), who ": bad image size W=%d H=%d", W, H);                          \
-    NM_REQUIRE(fx == fx && fy == fy && cx == cx && cy == cy, who ": NaN intrinsics")
 
 int nm_raster_mesh(nm_raster_t h, const float* verts, const double* w2c, double fx, double fy, double cx, double cy, int W, int H, int32_t* face_id,
                    float* zbuf, float* bary, nm_stream_t stream) {

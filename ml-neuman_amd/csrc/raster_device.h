@@ -1,0 +1,134 @@
+// What the mesh rasteriser (raster.hip) and the soft silhouette (silhouette.hip) share: the handle, the camera, the float64 vertex pass, the
+// exclusive scan of the per-tile counts and the edge functions that decide coverage.  Both files work on one nm_raster_t, so a pixel is
+// "inside" a face for the silhouette exactly when the rasteriser covers it.  Include after common.h.
+#pragma once
+#include "common.h"
+
+#include <math.h>
+
+namespace nm_rast {
+
+constexpr int kTile = 16;                    // pixels per tile side; kTile * kTile lanes per workgroup
+constexpr int kBatch = kTile * kTile;        // faces staged through LDS at a time
+constexpr float kNormEps = 1e-6f;            // torch.nn.functional.normalize's eps as pytorch3d calls it: x / max(|x|, eps)
+
+struct Cam {
+    double w2c[12];                          // row-major [3][4]
+    double fx, fy, cx, cy;
+};
+
+inline Cam make_cam(const double* w2c, double fx, double fy, double cx, double cy) {
+    Cam cam;
+    for (int i = 0; i < 12; ++i) cam.w2c[i] = w2c[i];
+    cam.fx = fx; cam.fy = fy; cam.cx = cx; cam.cy = cy;
+    return cam;
+}
+
+// ---- vertex pass ----------------------------------------------------------------------------------------------------------------------
+static __global__ void raster_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces, const int32_t* __restrict__ adj_off,
+                                            const int32_t* __restrict__ adj, int V, Cam cam, int want_normals, float4* __restrict__ vscr,
+                                            float* __restrict__ vnrm) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const double x = verts[3 * v], y = verts[3 * v + 1], z = verts[3 * v + 2];
+    const double xc = ((cam.w2c[0] * x + cam.w2c[1] * y) + cam.w2c[2] * z) + cam.w2c[3];
+    const double yc = ((cam.w2c[4] * x + cam.w2c[5] * y) + cam.w2c[6] * z) + cam.w2c[7];
+    const double zc = ((cam.w2c[8] * x + cam.w2c[9] * y) + cam.w2c[10] * z) + cam.w2c[11];
+    // a vertex at or behind the camera plane drops its faces whole (face setup reads the sign of .w); its screen position is never used
+    const bool front = zc > 0.0;
+    const double iz = front ? 1.0 / zc : 0.0;
+    vscr[v] = make_float4(front ? (float)(cam.fx * xc * iz + cam.cx) : 0.f, front ? (float)(cam.fy * yc * iz + cam.cy) : 0.f, (float)iz, (float)zc);
+    if (!want_normals) return;
+    double nx = 0.0, ny = 0.0, nz = 0.0;
+    for (int k = adj_off[v]; k < adj_off[v + 1]; ++k) {
+        const int f = adj[k];
+        const int i0 = faces[3 * f], i1 = faces[3 * f + 1], i2 = faces[3 * f + 2];
+        const double ax = (double)verts[3 * i1] - verts[3 * i0], ay = (double)verts[3 * i1 + 1] - verts[3 * i0 + 1], az = (double)verts[3 * i1 + 2] - verts[3 * i0 + 2];
+        const double bx = (double)verts[3 * i2] - verts[3 * i0], by = (double)verts[3 * i2 + 1] - verts[3 * i0 + 1], bz = (double)verts[3 * i2 + 2] - verts[3 * i0 + 2];
+        nx += ay * bz - az * by;
+        ny += az * bx - ax * bz;
+        nz += ax * by - ay * bx;
+    }
+    const double len = fmax(sqrt((nx * nx + ny * ny) + nz * nz), (double)kNormEps);
+    vnrm[3 * v] = (float)(nx / len);
+    vnrm[3 * v + 1] = (float)(ny / len);
+    vnrm[3 * v + 2] = (float)(nz / len);
+}
+
+// exclusive scan of the T tile counts by one workgroup: offset[0 .. T], offset[T] the total; cursor = offset[0 .. T-1] for the fill
+static __global__ void raster_scan_kernel(const int32_t* __restrict__ count, int T, int32_t* __restrict__ offset, int32_t* __restrict__ cursor) {
+    __shared__ int part[256];
+    const int per = (T + 255) / 256, lo = threadIdx.x * per, hi = min(lo + per, T);
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += count[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int i = 0; i < 256; ++i) { const int t = part[i]; part[i] = run; run += t; }
+        offset[T] = run;
+    }
+    __syncthreads();
+    int run = part[threadIdx.x];
+    for (int i = lo; i < hi; ++i) { offset[i] = run; cursor[i] = run; run += count[i]; }
+}
+
+// the three edge functions of the pixel centre, on vertices translated by it: w0 pairs (v1, v2), w1 (v2, v0), w2 (v0, v1)
+__device__ __forceinline__ void edge_functions(const float4 r0, const float4 r1, float px, float py, float& w0, float& w1, float& w2) {
+    const float ax = r0.x - px, ay = r0.y - py, bx = r0.z - px, by = r0.w - py, cx = r1.x - px, cy = r1.y - py;
+    w0 = bx * cy - by * cx;
+    w1 = cx * ay - cy * ax;
+    w2 = ax * by - ay * bx;
+}
+
+// rule 2's coverage test on those edge functions
+__device__ __forceinline__ bool covers(float w0, float w1, float w2) {
+    const float s = (w0 + w1) + w2;
+    return (s > 0.f && w0 >= 0.f && w1 >= 0.f && w2 >= 0.f) || (s < 0.f && w0 <= 0.f && w1 <= 0.f && w2 <= 0.f);
+}
+
+}  // namespace nm_rast
+
+struct nm_raster_s {
+    int F, V;
+    int32_t* d_faces;        // [F,3]
+    int32_t* d_adj_off;      // [V+1] vertex -> faces, CSR, ascending face id inside a vertex
+    int32_t* d_adj;          // [3F]
+    float4* d_vscr;          // [V] (u, v, 1/z, z)
+    float* d_vnrm;           // [V,3]
+    float4* d_rec;           // [F][3]
+    int4* d_box;             // [F]
+    int32_t* d_tiles;        // count [T], offset [T+1], cursor [T]: grown to the largest image seen
+    int tiles_cap;
+    int32_t* d_list;         // the tiles' face lists, end to end: grown to the largest total seen
+    int64_t list_cap;
+    float* d_gface;          // [F,3,2] the silhouette's screen-space gradient per face corner: made by the first backward call
+};
+
+namespace nm_rast {
+
+// the tile scratch of an image of T tiles and the face lists of `total` entries: both only ever grow
+inline int reserve_tiles(nm_raster_s* h, int T) {
+    if (T <= h->tiles_cap) return NM_OK;
+    if (h->d_tiles) (void)hipFree(h->d_tiles);
+    h->d_tiles = nullptr; h->tiles_cap = 0;
+    if (int rc = nm::check_hip(hipMalloc(&h->d_tiles, (size_t)(3 * T + 1) * 4), "raster: hipMalloc(tiles)")) return rc;
+    h->tiles_cap = T;
+    return NM_OK;
+}
+
+inline int reserve_lists(nm_raster_s* h, int64_t total) {
+    if (total <= h->list_cap) return NM_OK;
+    if (h->d_list) (void)hipFree(h->d_list);
+    h->d_list = nullptr; h->list_cap = 0;
+    if (int rc = nm::check_hip(hipMalloc(&h->d_list, (size_t)total * 4), "raster: hipMalloc(lists)")) return rc;
+    h->list_cap = total;
+    return NM_OK;
+}
+
+}  // namespace nm_rast
+
+#define NM_RASTER_ARGS(who)                                                                                                         \
+    NM_REQUIRE(h && verts && w2c, who ": null pointer");                                                                            \
+    NM_REQUIRE(W >= 1 && H >= 1 && (int64_t)W * H <= (1ll << 30), who ": bad image size W=%d H=%d", W, H);                          \
+    NM_REQUIRE(fx == fx && fy == fy && cx == cx && cy == cy, who ": NaN intrinsics")

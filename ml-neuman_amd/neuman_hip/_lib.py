@@ -209,6 +209,10 @@ SIGNATURES = {
     "nm_raster_phong": (i32, [ctypes.c_void_p, c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, i32, i32,
                               c_i32p, c_f32p, c_f32p, ctypes.POINTER(ctypes.c_double), c_f32p, c_stream]),
     "nm_overlay_rgba8": (i32, [c_f32p, ctypes.c_void_p, ctypes.c_void_p, i64, c_stream]),
+    "nm_raster_silhouette": (i32, [ctypes.c_void_p, c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                   i32, i32, ctypes.c_double, ctypes.c_double, c_f32p, c_f32p, c_i32p, c_stream]),
+    "nm_raster_silhouette_backward": (i32, [ctypes.c_void_p, c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                            ctypes.c_double, i32, i32, ctypes.c_double, ctypes.c_double, c_f32p, c_f32p, c_f32p, c_stream]),
 }
 
 _lib = None

@@ -2,9 +2,13 @@
 faces, the vertex -> face table of the normals and the passes' scratch on the device; `rasterizer_for(faces, V)` keeps the last few.
 
 The camera of a capture is read here too: intrinsics from `cap.pinhole_cam` (the reference's captures) or `cap.intrinsic_matrix`
-(synthetic.SimpleCapture), the world-to-camera matrix from `cap.cam_pose` in float64."""
+(synthetic.SimpleCapture), the world-to-camera matrix from `cap.cam_pose` in float64.
+
+The soft silhouette (csrc/silhouette.hip, the header's 'soft silhouette') works on the same handle: `Rasterizer.silhouette` and
+`silhouette_backward` are the two entries, `soft_silhouette` joins them under torch's autograd."""
 import collections
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -12,6 +16,12 @@ import torch
 from . import _lib
 
 LIGHT = (2.0, 2.0, -2.0)                                           # PointLights(location=...) of render_utils.py:469
+SIGMA = 1e-4                                                       # BlendParams(sigma=1e-4) of preprocess/optimize_smpl.py:89
+
+
+def default_blur_radius(sigma=SIGMA):
+    """preprocess/optimize_smpl.py:92: the squared NDC distance at which a face's probability has fallen to 1e-4"""
+    return math.log(1.0 / 1e-4 - 1.0) * sigma
 
 
 def camera_of(cap):
@@ -89,6 +99,63 @@ class Rasterizer:
                 _lib.check(_lib.lib().nm_raster_mesh(self._h, _lib.dev_ptr(verts), w2c_p, fx, fy, cx, cy, W, H, _lib.dev_ptr(face_id, torch.int32),
                                                      _lib.dev_ptr(zbuf), _lib.dev_ptr(bary), _lib.stream_ptr()), "nm_raster_mesh")
         return face_id, zbuf, bary, rgba
+
+    def silhouette(self, verts, camera, sigma=SIGMA, blur_radius=None, want_count=False):
+        """nm_raster_silhouette -> (alpha [H,W] f32, keep [H,W] f32 = 1 - alpha as the product left it, n_cand [H,W] int32 or None) on verts'
+        device; no graph is recorded (`soft_silhouette` is the differentiable form)."""
+        verts = self._verts(verts)
+        w2c, fx, fy, cx, cy, W, H = camera
+        if W < 1 or H < 1:
+            raise _lib.NeumanHipError(f"silhouette: empty image {W} x {H}")
+        blur_radius = default_blur_radius(sigma) if blur_radius is None else blur_radius
+        dev = verts.device
+        with torch.cuda.device(dev):
+            alpha = torch.empty((H, W), device=dev, dtype=torch.float32)
+            keep = torch.empty((H, W), device=dev, dtype=torch.float32)
+            n_cand = torch.empty((H, W), device=dev, dtype=torch.int32) if want_count else None
+            w2c, w2c_p = _f64(w2c)
+            _lib.check(_lib.lib().nm_raster_silhouette(self._h, _lib.dev_ptr(verts), w2c_p, fx, fy, cx, cy, W, H, float(sigma), float(blur_radius), _lib.dev_ptr(alpha),
+                                                       _lib.dev_ptr(keep), _lib.dev_ptr(n_cand, torch.int32), _lib.stream_ptr()), "nm_raster_silhouette")
+        return alpha, keep, n_cand
+
+    def silhouette_backward(self, verts, camera, sigma, blur_radius, keep, g_alpha):
+        """nm_raster_silhouette_backward: keep [H,W] of `silhouette` on the same arguments, g_alpha [H,W] = d loss / d alpha -> g_verts [V,3] f32"""
+        verts = self._verts(verts)
+        w2c, fx, fy, cx, cy, W, H = camera
+        keep, g_alpha = keep.detach().to(torch.float32).contiguous(), g_alpha.detach().to(torch.float32).contiguous()
+        if tuple(keep.shape) != (H, W) or tuple(g_alpha.shape) != (H, W) or keep.device != verts.device or g_alpha.device != verts.device:
+            raise _lib.NeumanHipError(f"silhouette_backward: keep {tuple(keep.shape)} and g_alpha {tuple(g_alpha.shape)} must be [{H}, {W}] on {verts.device}")
+        with torch.cuda.device(verts.device):
+            g_verts = torch.empty((self.V, 3), device=verts.device, dtype=torch.float32)
+            w2c, w2c_p = _f64(w2c)
+            _lib.check(_lib.lib().nm_raster_silhouette_backward(self._h, _lib.dev_ptr(verts), w2c_p, fx, fy, cx, cy, W, H, float(sigma), float(blur_radius),
+                                                                _lib.dev_ptr(keep), _lib.dev_ptr(g_alpha), _lib.dev_ptr(g_verts), _lib.stream_ptr()),
+                       "nm_raster_silhouette_backward")
+        return g_verts
+
+
+class _SilhouetteFn(torch.autograd.Function):
+    """alpha [H,W] of the soft silhouette as a function of verts [V,3]: the two entries of csrc/silhouette.hip.  The backward recomputes the
+    candidates from verts; keep is what the forward saved (rule S5)."""
+
+    @staticmethod
+    def forward(ctx, verts, rast, camera, sigma, blur_radius):
+        alpha, keep, _ = rast.silhouette(verts, camera, sigma, blur_radius)
+        ctx.rast, ctx.camera, ctx.sigma, ctx.blur_radius = rast, camera, sigma, blur_radius
+        ctx.save_for_backward(verts.detach(), keep)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, g_alpha):
+        verts, keep = ctx.saved_tensors
+        g = ctx.rast.silhouette_backward(verts, ctx.camera, ctx.sigma, ctx.blur_radius, keep, g_alpha)
+        return g.to(verts.dtype), None, None, None, None
+
+
+def soft_silhouette(rast, verts, camera, sigma=SIGMA, blur_radius=None):
+    """alpha [H,W] f32, differentiable with respect to verts [V,3] (a CUDA tensor)"""
+    rast._verts(verts)                                             # (refuses a CPU tensor or a wrong shape before autograd sees it)
+    return _SilhouetteFn.apply(verts, rast, camera, float(sigma), float(default_blur_radius(sigma) if blur_radius is None else blur_radius))
 
 
 _CACHE = collections.OrderedDict()

@@ -1421,3 +1421,14 @@ def overlay_smpl(img, verts, faces, cap):
         if image.dtype != torch.uint8:
             raise _lib.NeumanHipError(f"overlay_smpl: img must be uint8, got {image.dtype}")
         return raster.overlay_rgba(rgba, image[..., :3].contiguous().to(rgba.device)).cpu().numpy()
+
+
+def soft_silhouette(verts, faces, cap, sigma=1e-4, blur_radius=None):
+    """reference preprocess/optimize_smpl.py:84-102, 249-250: the body's soft silhouette as `cap` sees it -> alpha [H,W] f32 on the device,
+    differentiable with respect to verts [V,3] (CUDA f32).  blur_radius defaults to log(1/1e-4 - 1) sigma (:92).  Every face within the blur
+    radius counts, not the 100 nearest (the header's rule S4)."""
+    from . import raster
+    if not isinstance(verts, torch.Tensor) or not verts.is_cuda:
+        raise _lib.NeumanHipError("verts must be a CUDA (HIP) tensor: the silhouette has no CPU path")
+    _lib.require_gpu()
+    return raster.soft_silhouette(raster.rasterizer_for(faces, verts.shape[0]), verts, raster.camera_of(cap), sigma, blur_radius)

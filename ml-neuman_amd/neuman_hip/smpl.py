@@ -215,8 +215,9 @@ class SMPLDiff(torch.nn.Module):
         eye = torch.eye(3, dtype=rot_vecs.dtype, device=rot_vecs.device)[None]
         return eye + s * K + (1 - c) * torch.bmm(K, K)
 
-    def transformations(self, pose, beta):
-        """pose [1,J*3], beta [1,NB] -> (vertex transforms T [V,4,4] from the shaped template to the posed body, v_shaped [V,3])"""
+    def joint_transformations(self, pose, beta):
+        """pose [1,J*3], beta [1,NB] -> (joint transforms A [J,4,4] with the rest pose removed, rest joints [J,3], v_shaped [V,3]);
+        A_j applied to rest joint j is the posed joint (preprocess/optimize_smpl.py:111-117 reads them with concat_joints=True)"""
         J = len(self.parents_list)
         v_shaped = self.v_template + torch.einsum('vkl,l->vk', self.shapedirs, beta[0])            # smpl.py:312
         joints = self.J_regressor @ v_shaped                                                       # :315
@@ -233,6 +234,11 @@ class SMPLDiff(torch.nn.Module):
         shift = torch.einsum('jab,jb->ja', G[:, :3, :3], joints)
         A = G.clone()
         A[:, :3, 3] = G[:, :3, 3] - shift
+        return A, joints, v_shaped
+
+    def transformations(self, pose, beta):
+        """pose [1,J*3], beta [1,NB] -> (vertex transforms T [V,4,4] from the shaped template to the posed body, v_shaped [V,3])"""
+        A, _, v_shaped = self.joint_transformations(pose, beta)
         T = torch.einsum('vj,jab->vab', self.lbs_weights, A)                                        # :338-341
         return T, v_shaped
 
