@@ -516,6 +516,27 @@ int nm_smpl_vertex_forward(nm_smpl_t smpl, const float* pose, const float* beta,
 int nm_smpl_vertex_backward(nm_smpl_t smpl, const float* pose, const float* beta, const double* alignment, double scale, const float* da_pose,
                             const float* g_world, const float* g_T, float* workspace, float* g_pose, float* g_beta, float* g_align,
                             nm_stream_t stream);
+/* The same for B frames at once -- what a sequence's pose refinement needs (preprocess/optimize_smpl.py:259-295 refines every capture of a
+ * video; the frames are independent problems of one body model).  DEVICE pointers: poses [B,J*3], betas [B,NB] f32, alignments [B,4,4] f64,
+ * da_pose [J*3] f32 or null (one canonical pose for all frames).  The frame is a grid dimension of the one-frame kernels: three launches
+ * forward, seven backward (eight with g_joints), whatever B is.
+ *   forward:  world_out [B,V,3]; joints_out [B,J,3] = the world joints of the reference's vertext_forward (preprocess/optimize_smpl.py:105-130):
+ *             D(scale) align^T A_j [J_j; 1] with A_j the pose chain's joint transform and J_j the rest joint, float32; T_out [B,V,4,4] or null.
+ *   backward: g_world [B,V,3], g_joints [B,J,3], g_T [B,V,4,4], each nullable (= zero) but not all three -> g_pose [B,J*3], g_beta [B,NB],
+ *             g_align [B,4,4], written, not accumulated.
+ *   With g_joints null, frame b's world_out, g_pose, g_beta and g_align are the SAME BITS as the one-frame entries give on frame b's
+ *   inputs, whatever B is and wherever b sits: the same kernels run on the frame's slice.  joints_out and the terms g_joints adds are
+ *   float32 sums in a fixed order (run to run bit-identical).
+ *   workspace: nm_smpl_vertex_batch_workspace_floats(smpl, B) floats, the caller's: B x (38 J + 27 V + 24 J + 3 J + 48 ceil(V / 256)
+ *   + 15 J + 16) + 64; about 0.75 MB per frame for SMPL (V 6890, J 24).  No hidden allocation.
+ *   NM_ERR_ARG for a null pointer, B < 1 or B > 65535, or no upstream gradient. */
+int64_t nm_smpl_vertex_batch_workspace_floats(nm_smpl_t smpl, int B);
+int nm_smpl_vertex_forward_batch(nm_smpl_t smpl, const float* poses, const float* betas, const double* alignments, double scale,
+                                 const float* da_pose, int B, float* workspace, float* world_out, float* joints_out, float* T_out,
+                                 nm_stream_t stream);
+int nm_smpl_vertex_backward_batch(nm_smpl_t smpl, const float* poses, const float* betas, const double* alignments, double scale,
+                                  const float* da_pose, int B, const float* g_world, const float* g_joints, const float* g_T, float* workspace,
+                                  float* g_pose, float* g_beta, float* g_align, nm_stream_t stream);
 int nm_smpl_frames(nm_smpl_t smpl, const float* poses, const float* betas, const double* alignments, int B, double scale,
                    int precise, double* T_out, float* world_out, float* static_out, nm_stream_t stream);
 
@@ -807,6 +828,29 @@ int nm_raster_silhouette(nm_raster_t h, const float* verts, const double* w2c, d
 int nm_raster_silhouette_backward(nm_raster_t h, const float* verts, const double* w2c, double fx, double fy, double cx, double cy, int W,
                                   int H, double sigma, double blur_radius, const float* keep, const float* g_alpha, float* g_verts,
                                   nm_stream_t stream);
+/* The soft silhouette of B frames at once: one topology (the handle's) and one image size, each frame with its own vertices and camera.
+ *   Every array is a DEVICE pointer: verts [B,V,3] f32, w2c [B,4,4] f64 (row-major world-to-camera; rows 0-2 are used), intr [B,4] f64
+ *   (fx, fy, cx, cy); alpha, keep [B,H,W] f32, n_cand [B,H,W] int32 or null; backward: keep, g_alpha [B,H,W], g_verts [B,V,3] written,
+ *   not accumulated.
+ *   Rules S1-S6 hold unchanged, per frame, and frame b's alpha, keep, n_cand and g_verts are the SAME BITS as the one-frame entries give
+ *   on frame b's inputs, whatever B is and wherever b sits in the batch: the kernels are the one-frame kernels' bodies with the frame as
+ *   a grid dimension, every (frame, tile) list in ascending face order, no float atomics, the same summation orders.
+ *   Launches: forward six (vertex pass, face setup, count, scan, fill, blend), backward three, whatever B is.  The forward makes ONE
+ *   16-byte read-back per call (the lists' total length and the bad-camera word), the backward none.
+ *   List offsets are 64-bit: a batch's lists can pass 2^31 entries (some 630 candidates per pixel were measured on single frames).
+ *   Scratch, owned by the handle and grown to the largest batch seen (apart from the one-frame passes' scratch):
+ *     per frame  16 V + 48 F bytes (screen vertices, face records, boxes) + 12 ceil(W / 16) ceil(H / 16) (counts, offsets)
+ *                + 24 F once a backward has run (per-corner gradients): 0.81 MB, then 1.14 MB, for the 13 776-face body at 1280 x 720
+ *     per call   4 bytes per list entry (sum over the frames' tiles of the faces whose grown box touches the tile)
+ *   NM_ERR_ARG (with the entry's name in nm_last_error()) before any device work for a null pointer, B < 1 (or > 65535), W * H = 0,
+ *   sigma not finite or <= 0, blur_radius not finite or < 0.  A non-finite entry of a frame's w2c or intr is found on the device and
+ *   reported through the same read-back: the call returns NM_ERR_ARG naming the first such frame, after writing every frame's outputs
+ *   (such a frame has no candidates: alpha 0, keep 1; its g_verts are 0). */
+int nm_raster_silhouette_batch(nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H, double sigma,
+                               double blur_radius, float* alpha, float* keep, int32_t* n_cand, nm_stream_t stream);
+int nm_raster_silhouette_backward_batch(nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H,
+                                        double sigma, double blur_radius, const float* keep, const float* g_alpha, float* g_verts,
+                                        nm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * SURVEY 8f-1 (first slice): device primitives of a training step of the background NeRF --

@@ -205,7 +205,8 @@ extern "C" {
 
 int nm_raster_destroy(nm_raster_t h) {
     if (!h) return NM_OK;
-    void* bufs[] = {h->d_faces, h->d_adj_off, h->d_adj, h->d_vscr, h->d_vnrm, h->d_rec, h->d_box, h->d_tiles, h->d_list, h->d_gface};
+    void* bufs[] = {h->d_faces, h->d_adj_off, h->d_adj, h->d_vscr, h->d_vnrm, h->d_rec, h->d_box, h->d_tiles, h->d_list, h->d_gface, h->d_bvscr,
+                    h->d_brec, h->d_bbox, h->d_bcount, h->d_boffset, h->d_bgface};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete h;

@@ -25,11 +25,8 @@ inline Cam make_cam(const double* w2c, double fx, double fy, double cx, double c
 }
 
 // ---- vertex pass ----------------------------------------------------------------------------------------------------------------------
-static __global__ void raster_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces, const int32_t* __restrict__ adj_off,
-                                            const int32_t* __restrict__ adj, int V, Cam cam, int want_normals, float4* __restrict__ vscr,
-                                            float* __restrict__ vnrm) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= V) return;
+// rule 1 for one vertex: (u, v, 1/z, z); the one-frame and the batched passes both go through here, so they round alike
+__device__ __forceinline__ float4 project_vertex(const float* __restrict__ verts, int v, const Cam& cam) {
     const double x = verts[3 * v], y = verts[3 * v + 1], z = verts[3 * v + 2];
     const double xc = ((cam.w2c[0] * x + cam.w2c[1] * y) + cam.w2c[2] * z) + cam.w2c[3];
     const double yc = ((cam.w2c[4] * x + cam.w2c[5] * y) + cam.w2c[6] * z) + cam.w2c[7];
@@ -37,7 +34,15 @@ static __global__ void raster_vertex_kernel(const float* __restrict__ verts, con
     // a vertex at or behind the camera plane drops its faces whole (face setup reads the sign of .w); its screen position is never used
     const bool front = zc > 0.0;
     const double iz = front ? 1.0 / zc : 0.0;
-    vscr[v] = make_float4(front ? (float)(cam.fx * xc * iz + cam.cx) : 0.f, front ? (float)(cam.fy * yc * iz + cam.cy) : 0.f, (float)iz, (float)zc);
+    return make_float4(front ? (float)(cam.fx * xc * iz + cam.cx) : 0.f, front ? (float)(cam.fy * yc * iz + cam.cy) : 0.f, (float)iz, (float)zc);
+}
+
+static __global__ void raster_vertex_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces, const int32_t* __restrict__ adj_off,
+                                            const int32_t* __restrict__ adj, int V, Cam cam, int want_normals, float4* __restrict__ vscr,
+                                            float* __restrict__ vnrm) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    vscr[v] = project_vertex(verts, v, cam);
     if (!want_normals) return;
     double nx = 0.0, ny = 0.0, nz = 0.0;
     for (int k = adj_off[v]; k < adj_off[v + 1]; ++k) {
@@ -103,6 +108,16 @@ struct nm_raster_s {
     int32_t* d_list;         // the tiles' face lists, end to end: grown to the largest total seen
     int64_t list_cap;
     float* d_gface;          // [F,3,2] the silhouette's screen-space gradient per face corner: made by the first backward call
+    // the batched silhouette's scratch (silhouette.hip), apart from the one-frame passes': grown to the largest batch / image seen
+    int batch_cap;           // frames the three per-frame arrays hold
+    float4* d_bvscr;         // [B,V]
+    float4* d_brec;          // [B,F,2]
+    int4* d_bbox;            // [B,F]
+    int64_t btiles_cap;      // B * T entries
+    int32_t* d_bcount;       // [B*T]
+    int64_t* d_boffset;      // [B*T+1] | {total, first bad frame + 1}: 64-bit, a batch's lists can pass 2^31 entries
+    int gface_cap;           // frames d_bgface holds
+    float* d_bgface;         // [B,F,3,2]: made by the first batched backward call
 };
 
 namespace nm_rast {

@@ -169,8 +169,9 @@ __global__ __launch_bounds__(256) void smpl_rows_kernel(SmplDims d, int B, const
                                                         const float* __restrict__ lbs_weights, const float* __restrict__ betas,
                                                         const double* __restrict__ alignments, double scale, int precise,
                                                         const float* __restrict__ ws, double* __restrict__ T_out, float* __restrict__ world,
-                                                        float* __restrict__ stat, float* __restrict__ T32) {
-    // T32 != null (nm_smpl_vertex_forward): vertex rows only, T as float32 [B,V,16] into T32, world [B,V,3]; T_out / stat unused
+                                                        float* __restrict__ stat, int vf, float* __restrict__ T32, float* __restrict__ joints_out) {
+    // vf (nm_smpl_vertex_forward and its batch): vertex rows give world [B,V,3] and, where T32 is given, T as float32 [B,V,16]; joint rows
+    // give joints_out [B,J,3] where it is given: D(scale) align^T A_j [J_j; 1], float32; T_out / stat unused
     const int rows = d.V + d.J;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (int64_t)B * rows) return;
@@ -178,6 +179,21 @@ __global__ __launch_bounds__(256) void smpl_rows_kernel(SmplDims d, int B, const
     const float* w = ws + (size_t)b * ws_floats(d.J);
     const float* A_pose = w + d.J * 6;
     const float* A_da = A_pose + d.J * 16;
+    if (vf && r >= d.V) {
+        if (!joints_out) return;
+        const int j = r - d.V;
+        const float* A = A_pose + j * 16;
+        const float* Jr = w + j * 3;
+        const double* al = alignments + (size_t)b * 16;
+        const float sc = (float)scale;
+        float pj[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pj[k] = A[k * 4] * Jr[0] + A[k * 4 + 1] * Jr[1] + A[k * 4 + 2] * Jr[2] + A[k * 4 + 3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+            joints_out[((size_t)b * d.J + j) * 3 + i] = sc * ((float)al[0 * 4 + i] * pj[0] + (float)al[1 * 4 + i] * pj[1] + (float)al[2 * 4 + i] * pj[2] + (float)al[3 * 4 + i]);
+        return;
+    }
     float Tp[16], Td[16], pt[3], dap[3];
     if (r < d.V) {
         // T = W A (smpl.py:343-344), both poses; v_shaped (:309); the da-pose vertex T_da [v_shaped; 1] (:355-358)
@@ -236,12 +252,13 @@ __global__ __launch_bounds__(256) void smpl_rows_kernel(SmplDims d, int B, const
                 T[i * 4 + j] = (double)(i < 3 ? sc * t : t);
             }
     }
-    if (T32) {
-        if (r >= d.V) return;
-        float* To = T32 + ((size_t)b * d.V + r) * 16;
+    if (vf) {
         float* wo = world + ((size_t)b * d.V + r) * 3;
+        if (T32) {
+            float* To = T32 + ((size_t)b * d.V + r) * 16;
 #pragma unroll
-        for (int q = 0; q < 16; ++q) To[q] = (float)T[q];
+            for (int q = 0; q < 16; ++q) To[q] = (float)T[q];
+        }
 #pragma unroll
         for (int k = 0; k < 3; ++k) wo[k] = (float)T[k * 4] * dap[0] + (float)T[k * 4 + 1] * dap[1] + (float)T[k * 4 + 2] * dap[2] + (float)T[k * 4 + 3] * 1.f;
         return;
@@ -270,6 +287,8 @@ __global__ __launch_bounds__(256) void smpl_jreg_kernel(SmplDims d, const float*
     __shared__ float beta[kMaxBetas];
     __shared__ float red[4][3];
     const int j = blockIdx.x, tid = threadIdx.x;
+    betas += (size_t)blockIdx.y * d.NB;                                  // frame blockIdx.y of a batch: its own shape and workspace
+    ws += (size_t)blockIdx.y * ws_floats(d.J);
     if (tid < d.NB) beta[tid] = betas[tid];
     __syncthreads();
     float acc[3] = {0.f, 0.f, 0.f};
@@ -298,6 +317,8 @@ __global__ __launch_bounds__(128) void smpl_chain_kernel(SmplDims d, const int32
     __shared__ float Rm[2][kMaxJoints][9];
     __shared__ float chain[2][kMaxJoints][16];
     const int tid = threadIdx.x;
+    pose += (size_t)blockIdx.x * d.J * 3;                                // frame blockIdx.x of a batch
+    ws += (size_t)blockIdx.x * ws_floats(d.J);
     for (int i = tid; i < d.J * 3; i += blockDim.x) Js[i / 3][i % 3] = ws[i];
     if (tid < 2 * d.J) {
         const int set = tid / d.J, j = tid % d.J;
@@ -349,6 +370,10 @@ __global__ __launch_bounds__(128) void smpl_chain_kernel(SmplDims d, const int32
 //   world = T [da; 1],  T = D(scale) align^T Tp inv(Td),  da = Td [v_shaped; 1],  Tp = sum_j w_j A_pose_j,  Td = sum_j w_j A_da_j,
 //   A_j = [G_j.R | G_j.t - G_j.R J_j],  G_j = G_parent [R_j | J_j - J_parent],  R_j = Rodrigues(pose_j),  J = J_regressor v_shaped,
 //   v_shaped = v_template + shapedirs beta.
+// The batch (nm_smpl_vertex_forward_batch / _backward_batch: the frames of a sequence) runs the same kernels with the frame as a grid dimension
+// -- blockIdx.y where a kernel is per vertex or per joint, blockIdx.x where it is one workgroup per frame -- and every region of the workspace
+// [B] of the one-frame one; the one-frame entries are its B = 1.  The world joints D(scale) align^T A_j [J_j; 1] of the reference's
+// vertext_forward come from the row kernel's joint rows, their gradient from smpl_bw_jointgrad_kernel (batch only).
 // ---- per vertex: gradients of Tp and Td (3 x 4 each: the last row of an affine blend is constant), of v_shaped through the da
 // vertex, and this vertex's share of the alignment gradient
 __global__ __launch_bounds__(256) void smpl_bw_rows_kernel(SmplDims d, const float* __restrict__ v_template, const float* __restrict__ shapedirs,
@@ -356,8 +381,15 @@ __global__ __launch_bounds__(256) void smpl_bw_rows_kernel(SmplDims d, const flo
                                                            const double* __restrict__ alignment, float sc, const float* __restrict__ ws,
                                                            const float* __restrict__ g_world, const float* __restrict__ g_T,
                                                            float* __restrict__ g_rows, float* __restrict__ g_al_part) {
-    // g_rows [V][27] = gTp (12) | gTd (12) | g v_shaped through da (3);  g_al_part [blocks][16]
+    // g_rows [V][27] = gTp (12) | gTd (12) | g v_shaped through da (3);  g_al_part [blocks][16]; frame blockIdx.y of a batch has its own of each
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    {
+        const size_t b = blockIdx.y;
+        beta += b * d.NB; alignment += b * 16; ws += b * ws_floats(d.J);
+        if (g_world) g_world += b * d.V * 3;
+        if (g_T) g_T += b * d.V * 16;
+        g_rows += b * d.V * 27; g_al_part += b * gridDim.x * 16;
+    }
     float gal[16];
 #pragma unroll
     for (int q = 0; q < 16; ++q) gal[q] = 0.f;
@@ -475,8 +507,12 @@ __global__ __launch_bounds__(256) void smpl_bw_rows_kernel(SmplDims d, const flo
 
 // ---- per (chain, joint): gA_j = sum_v w_vj gT_v (12 values), one workgroup each
 __global__ __launch_bounds__(256) void smpl_bw_joints_kernel(SmplDims d, const float* __restrict__ lbs_weights, const float* __restrict__ g_rows,
-                                                             float* __restrict__ g_A) {
+                                                             const float* __restrict__ g_jA, float* __restrict__ g_A) {
+    // g_jA [J][12] or null: what the joints' own gradient adds to the pose chain's g_A (smpl_bw_jointgrad_kernel)
     const int c = blockIdx.x / d.J, j = blockIdx.x % d.J;
+    g_rows += (size_t)blockIdx.y * d.V * 27;                             // frame blockIdx.y of a batch
+    g_A += (size_t)blockIdx.y * 2 * d.J * 12;
+    if (g_jA) g_jA += (size_t)blockIdx.y * d.J * 12;
     float acc[12];
 #pragma unroll
     for (int q = 0; q < 12; ++q) acc[q] = 0.f;
@@ -495,7 +531,11 @@ __global__ __launch_bounds__(256) void smpl_bw_joints_kernel(SmplDims d, const f
 #pragma unroll
         for (int q = 0; q < 12; ++q) red[threadIdx.x >> 6][q] = acc[q];
     __syncthreads();
-    if (threadIdx.x < 12) g_A[((size_t)c * d.J + j) * 12 + threadIdx.x] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    if (threadIdx.x < 12) {
+        float s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        if (g_jA && c == 0) s += g_jA[j * 12 + threadIdx.x];
+        g_A[((size_t)c * d.J + j) * 12 + threadIdx.x] = s;
+    }
 }
 
 // d Rodrigues: R = I + sin(t) K + (1 - cos t) K^2, K = skew(r / t), t = |r + 1e-8|  (smpl.py:407-438)
@@ -534,9 +574,16 @@ __device__ __forceinline__ void rodrigues_backward(const float* __restrict__ rv,
 // ---- one workgroup: the two kinematic chains backwards (children before parents) -> g pose [J*3] (pose chain only), g J [J,3]
 __global__ __launch_bounds__(64) void smpl_bw_chain_kernel(SmplDims d, const int32_t* __restrict__ parents, const float* __restrict__ pose,
                                                            const float* __restrict__ da_pose, const float* __restrict__ ws,
-                                                           const float* __restrict__ g_A, float* __restrict__ g_pose, float* __restrict__ g_J) {
+                                                           const float* __restrict__ g_A, const float* __restrict__ g_jJ, float* __restrict__ g_pose,
+                                                           float* __restrict__ g_J) {
+    // g_jJ [J][3] or null: the joints' own gradient to the rest joints they are applied to (smpl_bw_jointgrad_kernel)
     __shared__ float gJs[2][kMaxJoints][3];
     __shared__ float gGR[2][kMaxJoints][9], gGt[2][kMaxJoints][3];
+    {
+        const size_t b = blockIdx.x;                                     // frame blockIdx.x of a batch
+        pose += b * d.J * 3; ws += b * ws_floats(d.J); g_A += b * 2 * d.J * 12; g_pose += b * d.J * 3; g_J += b * d.J * 3;
+        if (g_jJ) g_jJ += b * d.J * 3;
+    }
     const int c = threadIdx.x;                                           // chain 0: the frame's pose, chain 1: the da pose
     if (c < 2) {
         const float* Js = ws;                                            // rest joints [J,3]
@@ -591,7 +638,11 @@ __global__ __launch_bounds__(64) void smpl_bw_chain_kernel(SmplDims d, const int
         }
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < d.J * 3; i += blockDim.x) g_J[i] = gJs[0][i / 3][i % 3] + gJs[1][i / 3][i % 3];
+    for (int i = threadIdx.x; i < d.J * 3; i += blockDim.x) {
+        float s = gJs[0][i / 3][i % 3] + gJs[1][i / 3][i % 3];
+        if (g_jJ) s += g_jJ[i];
+        g_J[i] = s;
+    }
 }
 
 // ---- per vertex: g v_shaped = (through the da vertex) + J_regressor^T g J;  g beta = shapedirs^T g v_shaped, block partials
@@ -599,6 +650,9 @@ __global__ __launch_bounds__(256) void smpl_bw_shape_kernel(SmplDims d, const fl
                                                             const float* __restrict__ g_rows, const float* __restrict__ g_J,
                                                             float* __restrict__ g_beta_part) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    g_rows += (size_t)blockIdx.y * d.V * 27;                             // frame blockIdx.y of a batch
+    g_J += (size_t)blockIdx.y * d.J * 3;
+    g_beta_part += (size_t)blockIdx.y * gridDim.x * kMaxBetas;
     float gb[kMaxBetas];
 #pragma unroll
     for (int l = 0; l < kMaxBetas; ++l) gb[l] = 0.f;
@@ -624,16 +678,70 @@ __global__ __launch_bounds__(256) void smpl_bw_shape_kernel(SmplDims d, const fl
 
 // ---- the block partials of the alignment and shape gradients, added in block order
 __global__ void smpl_bw_finish_kernel(int nblocks, int NB, const float* __restrict__ g_al_part, const float* __restrict__ g_beta_part,
-                                      float* __restrict__ g_align, float* __restrict__ g_beta) {
+                                      const float* __restrict__ g_jal, float* __restrict__ g_align, float* __restrict__ g_beta) {
+    // g_jal [16] or null: the joints' own gradient to the alignment (smpl_bw_jointgrad_kernel)
     const int t = threadIdx.x;
+    {
+        const size_t f = blockIdx.x;                                     // frame blockIdx.x of a batch
+        g_al_part += f * nblocks * 16; g_beta_part += f * nblocks * kMaxBetas; g_align += f * 16; g_beta += f * NB;
+        if (g_jal) g_jal += f * 16;
+    }
     if (t < 16) {
         float s = 0.f;
         for (int b = 0; b < nblocks; ++b) s += g_al_part[(size_t)b * 16 + t];
+        if (g_jal) s += g_jal[t];
         g_align[t] = s;
     } else if (t - 16 < NB) {
         float s = 0.f;
         for (int b = 0; b < nblocks; ++b) s += g_beta_part[(size_t)b * NB + (t - 16)];
         g_beta[t - 16] = s;
+    }
+}
+
+// ---- the world joints' gradient (batch only): joint_b,j = D(sc) align_b^T A_j [J_j; 1] with A_j the pose chain's.  One workgroup per
+// frame, one lane per joint -> g_jA [B,J,12] (to A_j), g_jJ [B,J,3] (to the rest joint it is applied to), g_jal [B,16] (to the alignment, the
+// joints added in index order).  The three are added where the vertices' gradients to A, J and the alignment are finished.
+__global__ __launch_bounds__(kMaxJoints) void smpl_bw_jointgrad_kernel(SmplDims d, const double* __restrict__ alignments, float sc,
+                                                                        const float* __restrict__ ws, const float* __restrict__ g_joints,
+                                                                        float* __restrict__ g_jA, float* __restrict__ g_jJ, float* __restrict__ g_jal) {
+    __shared__ float s_al[kMaxJoints][16];
+    const int j = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const float* w = ws + b * ws_floats(d.J);
+    float al[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) al[q] = (float)alignments[b * 16 + q];
+    if (j < d.J) {
+        const float* A = w + d.J * 6 + j * 16;
+        const float* Jr = w + j * 3;
+        const float* gj = g_joints + (b * d.J + j) * 3;
+        float pj[3], gpj[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            pj[k] = A[k * 4] * Jr[0] + A[k * 4 + 1] * Jr[1] + A[k * 4 + 2] * Jr[2] + A[k * 4 + 3];
+            gpj[k] = sc * (al[k * 4] * gj[0] + al[k * 4 + 1] * gj[1] + al[k * 4 + 2] * gj[2]);
+        }
+        float* oA = g_jA + (b * d.J + j) * 12;
+        float* oJ = g_jJ + (b * d.J + j) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) oA[k * 4 + c] = gpj[k] * Jr[c];
+            oA[k * 4 + 3] = gpj[k];
+            oJ[k] = A[k] * gpj[0] + A[4 + k] * gpj[1] + A[8 + k] * gpj[2];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) s_al[j][k * 4 + i] = sc * gj[i] * (k < 3 ? pj[k] : 1.f);
+            s_al[j][k * 4 + 3] = 0.f;
+        }
+    }
+    __syncthreads();
+    if (j < 16) {
+        float s = 0.f;
+        for (int q = 0; q < d.J; ++q) s += s_al[q][j];
+        g_jal[b * 16 + j] = s;
     }
 }
 
@@ -703,7 +811,7 @@ int nm_smpl_frames(nm_smpl_t m, const float* poses, const float* betas, const do
     if (int rc = nm::check_launch("smpl_joints_kernel")) return rc;
     const int64_t n = (int64_t)B * (m->d.V + m->d.J);
     hipLaunchKernelGGL(smpl_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->d, B, m->v_template, m->shapedirs, m->weights, betas,
-                       alignments, scale, precise, m->ws, T_out, world_out, static_out, nullptr);
+                       alignments, scale, precise, m->ws, T_out, world_out, static_out, 0, nullptr, nullptr);
     return nm::check_launch("smpl_rows_kernel");
 }
 
@@ -724,7 +832,7 @@ int nm_smpl_vertex_forward(nm_smpl_t m, const float* pose, const float* beta, co
     if (int rc = nm::check_launch("smpl_chain_kernel")) return rc;
     const int64_t n = m->d.V + m->d.J;
     hipLaunchKernelGGL(smpl_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->d, 1, m->v_template, m->shapedirs, m->weights, beta,
-                       alignment, scale, 0, workspace, nullptr, world_out, nullptr, T_out);
+                       alignment, scale, 0, workspace, nullptr, world_out, nullptr, 1, T_out, nullptr);
     return nm::check_launch("smpl_rows_kernel");
 }
 
@@ -750,14 +858,80 @@ int nm_smpl_vertex_backward(nm_smpl_t m, const float* pose, const float* beta, c
     hipLaunchKernelGGL(smpl_bw_rows_kernel, dim3(blocks), dim3(256), 0, st, d, m->v_template, m->shapedirs, m->weights, beta, alignment, (float)scale, ws,
                        g_world, g_T, g_rows, g_al_part);
     if (int rc = nm::check_launch("smpl_bw_rows_kernel")) return rc;
-    hipLaunchKernelGGL(smpl_bw_joints_kernel, dim3(2 * d.J), dim3(256), 0, st, d, m->weights, g_rows, g_A);
+    hipLaunchKernelGGL(smpl_bw_joints_kernel, dim3(2 * d.J), dim3(256), 0, st, d, m->weights, g_rows, (const float*)nullptr, g_A);
     if (int rc = nm::check_launch("smpl_bw_joints_kernel")) return rc;
-    hipLaunchKernelGGL(smpl_bw_chain_kernel, dim3(1), dim3(64), 0, st, d, m->parents, pose, dap, ws, g_A, g_pose, g_J);
+    hipLaunchKernelGGL(smpl_bw_chain_kernel, dim3(1), dim3(64), 0, st, d, m->parents, pose, dap, ws, g_A, (const float*)nullptr, g_pose, g_J);
     if (int rc = nm::check_launch("smpl_bw_chain_kernel")) return rc;
     hipLaunchKernelGGL(smpl_bw_shape_kernel, dim3(blocks), dim3(256), 0, st, d, m->shapedirs, m->j_reg, g_rows, g_J, g_beta_part);
     if (int rc = nm::check_launch("smpl_bw_shape_kernel")) return rc;
-    hipLaunchKernelGGL(smpl_bw_finish_kernel, dim3(1), dim3(64), 0, st, blocks, d.NB, g_al_part, g_beta_part, g_align, g_beta);
+    hipLaunchKernelGGL(smpl_bw_finish_kernel, dim3(1), dim3(64), 0, st, blocks, d.NB, g_al_part, g_beta_part, (const float*)nullptr, g_align, g_beta);
     return nm::check_launch("nm_smpl_vertex_backward");
+}
+
+// ---- the batch: B frames through the same kernels, the frame a grid dimension; every region of the workspace is [B] of the one-frame one
+int64_t nm_smpl_vertex_batch_workspace_floats(nm_smpl_t m, int B) {
+    if (!m || B < 1) return 0;
+    const int64_t blocks = (m->d.V + 255) / 256;
+    // joints workspaces | g_rows [B,V,27] | g_A [B,2,J,12] | g_J [B,J,3] | alignment partials | shape partials | g_jA [B,J,12] | g_jJ [B,J,3] | g_jal [B,16]
+    return (int64_t)B * (ws_floats(m->d.J) + (int64_t)m->d.V * 27 + 2 * m->d.J * 12 + m->d.J * 3 + blocks * 16 + blocks * kMaxBetas + m->d.J * 12 +
+                         m->d.J * 3 + 16) + 64;
+}
+
+int nm_smpl_vertex_forward_batch(nm_smpl_t m, const float* poses, const float* betas, const double* alignments, double scale, const float* da_pose, int B,
+                                 float* workspace, float* world_out, float* joints_out, float* T_out, nm_stream_t stream) {
+    NM_REQUIRE(m && poses && betas && alignments && workspace && world_out && joints_out, "nm_smpl_vertex_forward_batch: null pointer");
+    NM_REQUIRE(B >= 1 && B <= 65535, "nm_smpl_vertex_forward_batch: B = %d frames (1 <= B <= 65535)", B);
+    hipStream_t st = nm::as_stream(stream);
+    hipLaunchKernelGGL(smpl_jreg_kernel, dim3(m->d.J, B), dim3(256), 0, st, m->d, m->v_template, m->shapedirs, m->j_reg, betas, workspace);
+    if (int rc = nm::check_launch("smpl_jreg_kernel")) return rc;
+    hipLaunchKernelGGL(smpl_chain_kernel, dim3(B), dim3(128), 0, st, m->d, m->parents, poses, da_pose ? da_pose : m->da_pose, workspace);
+    if (int rc = nm::check_launch("smpl_chain_kernel")) return rc;
+    const int64_t n = (int64_t)B * (m->d.V + m->d.J);
+    hipLaunchKernelGGL(smpl_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m->d, B, m->v_template, m->shapedirs, m->weights, betas,
+                       alignments, scale, 0, workspace, nullptr, world_out, nullptr, 1, T_out, joints_out);
+    return nm::check_launch("smpl_rows_kernel");
+}
+
+int nm_smpl_vertex_backward_batch(nm_smpl_t m, const float* poses, const float* betas, const double* alignments, double scale, const float* da_pose, int B,
+                                  const float* g_world, const float* g_joints, const float* g_T, float* workspace, float* g_pose, float* g_beta,
+                                  float* g_align, nm_stream_t stream) {
+    NM_REQUIRE(m && poses && betas && alignments && workspace && g_pose && g_beta && g_align, "nm_smpl_vertex_backward_batch: null pointer");
+    NM_REQUIRE(B >= 1 && B <= 65535, "nm_smpl_vertex_backward_batch: B = %d frames (1 <= B <= 65535)", B);
+    NM_REQUIRE(g_world || g_T || g_joints, "nm_smpl_vertex_backward_batch: no upstream gradient");
+    hipStream_t st = nm::as_stream(stream);
+    const SmplDims d = m->d;
+    const int blocks = (d.V + 255) / 256;
+    const size_t nb = (size_t)B;
+    float* ws = workspace;
+    float* g_rows = ws + nb * ws_floats(d.J);
+    float* g_A = g_rows + nb * d.V * 27;
+    float* g_J = g_A + nb * 2 * d.J * 12;
+    float* g_al_part = g_J + nb * d.J * 3;
+    float* g_beta_part = g_al_part + nb * blocks * 16;
+    float* g_jA = g_beta_part + nb * blocks * kMaxBetas;
+    float* g_jJ = g_jA + nb * d.J * 12;
+    float* g_jal = g_jJ + nb * d.J * 3;
+    if (!g_joints) g_jA = g_jJ = g_jal = nullptr;
+    const float* dap = da_pose ? da_pose : m->da_pose;
+    hipLaunchKernelGGL(smpl_jreg_kernel, dim3(d.J, B), dim3(256), 0, st, d, m->v_template, m->shapedirs, m->j_reg, betas, ws);
+    if (int rc = nm::check_launch("smpl_jreg_kernel")) return rc;
+    hipLaunchKernelGGL(smpl_chain_kernel, dim3(B), dim3(128), 0, st, d, m->parents, poses, dap, ws);
+    if (int rc = nm::check_launch("smpl_chain_kernel")) return rc;
+    if (g_joints) {
+        hipLaunchKernelGGL(smpl_bw_jointgrad_kernel, dim3(B), dim3(kMaxJoints), 0, st, d, alignments, (float)scale, ws, g_joints, g_jA, g_jJ, g_jal);
+        if (int rc = nm::check_launch("smpl_bw_jointgrad_kernel")) return rc;
+    }
+    hipLaunchKernelGGL(smpl_bw_rows_kernel, dim3(blocks, B), dim3(256), 0, st, d, m->v_template, m->shapedirs, m->weights, betas, alignments, (float)scale, ws,
+                       g_world, g_T, g_rows, g_al_part);
+    if (int rc = nm::check_launch("smpl_bw_rows_kernel")) return rc;
+    hipLaunchKernelGGL(smpl_bw_joints_kernel, dim3(2 * d.J, B), dim3(256), 0, st, d, m->weights, g_rows, (const float*)g_jA, g_A);
+    if (int rc = nm::check_launch("smpl_bw_joints_kernel")) return rc;
+    hipLaunchKernelGGL(smpl_bw_chain_kernel, dim3(B), dim3(64), 0, st, d, m->parents, poses, dap, ws, g_A, (const float*)g_jJ, g_pose, g_J);
+    if (int rc = nm::check_launch("smpl_bw_chain_kernel")) return rc;
+    hipLaunchKernelGGL(smpl_bw_shape_kernel, dim3(blocks, B), dim3(256), 0, st, d, m->shapedirs, m->j_reg, g_rows, g_J, g_beta_part);
+    if (int rc = nm::check_launch("smpl_bw_shape_kernel")) return rc;
+    hipLaunchKernelGGL(smpl_bw_finish_kernel, dim3(B), dim3(64), 0, st, blocks, d.NB, g_al_part, g_beta_part, (const float*)g_jal, g_align, g_beta);
+    return nm::check_launch("nm_smpl_vertex_backward_batch");
 }
 
 }  // extern "C"

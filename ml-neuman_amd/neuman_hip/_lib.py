@@ -124,6 +124,11 @@ SIGNATURES = {
     "nm_smpl_vertex_forward": (i32, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_double, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "nm_smpl_vertex_backward": (i32, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_double, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                       c_f32p, c_f32p, c_stream]),
+    "nm_smpl_vertex_batch_workspace_floats": (i64, [ctypes.c_void_p, i32]),
+    "nm_smpl_vertex_forward_batch": (i32, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_double, c_f32p, i32, c_f32p, c_f32p, c_f32p, c_f32p,
+                                           c_stream]),
+    "nm_smpl_vertex_backward_batch": (i32, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_void_p, ctypes.c_double, c_f32p, i32, c_f32p, c_f32p, c_f32p, c_f32p,
+                                            c_f32p, c_f32p, c_f32p, c_stream]),
     "nm_smpl_frames": (i32, [ctypes.c_void_p, c_f32p, c_f32p, ctypes.c_void_p, i32, ctypes.c_double, i32, ctypes.c_void_p, c_f32p, c_f32p,
                              c_stream]),
     "nm_gemm_workspace_floats": (i64, [i32, i32, i32]),
@@ -213,6 +218,10 @@ SIGNATURES = {
                                    i32, i32, ctypes.c_double, ctypes.c_double, c_f32p, c_f32p, c_i32p, c_stream]),
     "nm_raster_silhouette_backward": (i32, [ctypes.c_void_p, c_f32p, ctypes.POINTER(ctypes.c_double), ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                             ctypes.c_double, i32, i32, ctypes.c_double, ctypes.c_double, c_f32p, c_f32p, c_f32p, c_stream]),
+    "nm_raster_silhouette_batch": (i32, [ctypes.c_void_p, c_f32p, ctypes.c_void_p, ctypes.c_void_p, i32, i32, i32, ctypes.c_double, ctypes.c_double, c_f32p,
+                                         c_f32p, c_i32p, c_stream]),
+    "nm_raster_silhouette_backward_batch": (i32, [ctypes.c_void_p, c_f32p, ctypes.c_void_p, ctypes.c_void_p, i32, i32, i32, ctypes.c_double, ctypes.c_double,
+                                                  c_f32p, c_f32p, c_f32p, c_stream]),
 }
 
 _lib = None

@@ -9,7 +9,15 @@ The reference renders the body's soft silhouette with pytorch3d (:84-102); here 
 include/neuman_hip.h 'soft silhouette': every face within the blur radius counts, not the 100 nearest).  The body is skinned by the
 hand-written kernels of `SMPLDiff.vertex_forward`; the 24 joints, which are tiny, go through SMPLDiff's tensor algebra.  The file handling of the
 reference's main() / dump_visualizations() is not here: `data_io.py` reads what they read.
+
+    main's loop over the captures                                   :277-293    optimize_scene, over optimize_smpl_sequence
+
+A video's frames are independent problems of one topology and one image size: `optimize_smpl_sequence` fits `frames_per_batch` of them at a
+time on the batched kernels (`SMPLDiff.vertex_forward_batch`, `render_utils.soft_silhouette_batch`), a handful of launches and one host read per
+iteration whatever the number of frames, and every frame takes exactly the steps it would take alone.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -166,3 +174,140 @@ def optimize_smpl(cap, smpl, faces, body_model, align, scale, num_iters=100, sig
         pose.grad = pose.grad * grad_mask * valid_mask
         optim.step()
     return pose.detach().cpu().numpy()
+
+
+def _alignment_of(alignments, cap, i):
+    """the frame's [4,3] alignment: `alignments` is main()'s dict keyed by the image's file name (:269, :289), or one per capture in order"""
+    if isinstance(alignments, dict):
+        return alignments[os.path.basename(cap.image_path)]
+    return alignments[i]
+
+
+class SequenceObjective:
+    """The sum over the captures of `Objective.loss`, every frame with its own normalisers (the mean over ITS confident joints, the mean over
+    ITS pixels): only the sum is across frames, so row b of the gradient with respect to poses [B,72] is the gradient of frame b's own loss.
+    On float32 CUDA poses the skinning and the silhouette are the batched kernels and everything between them is elementwise in the frame
+    (no reduction or matrix product whose order could depend on B); elsewhere (the float64 restatement the tests check against) the
+    skinning is `vertext_forward` frame by frame.  `silhouette(world_verts [B,V,3]) -> alpha [B,H,W]` is `render_utils.soft_silhouette_batch`
+    unless given.  Every per-frame input is stacked on the host and uploaded once, here."""
+
+    def __init__(self, caps, smpls, faces, body_model, alignments, scale, sigma=1e-4, silhouette=None):
+        self.body_model, self.scale, self.B = body_model, scale, len(caps)
+        ref = body_model.v_template
+        dev, dt = ref.device, ref.dtype
+        npdt = np.float32 if dt == torch.float32 else np.float64
+        cams = [raster.camera_of(cap) for cap in caps]
+        sizes = sorted({(c[5], c[6]) for c in cams})
+        if len(sizes) != 1:
+            raise ValueError(f"the captures of a sequence fit must share one image size, got (W, H) = {sizes}: group them by size")
+        W, H = sizes[0]
+        self.shape = (H, W)
+        aligns, targets, P = [], [], []
+        for i, (cap, cam) in enumerate(zip(caps, cams)):
+            temp = np.eye(4)
+            temp[..., :3] = np.asarray(_alignment_of(alignments, cap, i))
+            aligns.append(temp)
+            keypoints = np.array(cap.keypoints, dtype=np.float64)
+            joints_target = keypoints[:, :2]
+            joints_target[keypoints[:, 2] < 0.3] = 0
+            targets.append(coco_to_smpl(joints_target))
+            K = np.array([[cam[1], 0., cam[3]], [0., cam[2], cam[4]], [0., 0., 1.]])
+            P.append(K.astype(npdt) @ cam[0].astype(npdt))                                         # K w2c, [3,4], in the objective's precision
+        up = lambda a: torch.as_tensor(np.stack(a)).to(dev, dt)                                    # noqa: E731
+        self.betas = up([np.asarray(s['betas']).reshape(-1) for s in smpls])
+        self.align = up(aligns)
+        self.mask_target = up([np.asarray(cap.binary_mask) for cap in caps])
+        self.joints_target = up(targets)
+        self.joints_mask = (self.joints_target.sum(dim=2) != 0).to(dt)                             # [B,24]
+        self.joints_count = self.joints_mask.sum(dim=1).clamp(min=1) * 2                           # (x and y; a frame without a confident joint divides 0 by 2)
+        self.P = up(P)
+        if isinstance(faces, torch.Tensor):
+            faces = faces.detach().cpu().numpy()
+        if silhouette is None:
+            cameras = raster.batch_cameras(caps, dev)
+            silhouette = lambda v: render_utils.soft_silhouette_batch(v, faces, cameras, sigma)     # noqa: E731
+        self.silhouette = silhouette
+
+    def forward_bodies(self, poses):
+        """-> world_verts [B,V,3], world_joints [B,24,3]"""
+        if poses.is_cuda and poses.dtype == torch.float32 and isinstance(self.scale, (int, float)):
+            return self.body_model.vertex_forward_batch(poses, self.betas, self.align, float(self.scale), da_pose=torch.zeros_like(poses[:1]))
+        out = [vertext_forward(poses[b], self.betas[b], self.align[b], self.body_model, self.scale) for b in range(self.B)]
+        return torch.cat([o[0] for o in out]), torch.cat([o[1] for o in out])
+
+    def project(self, world_joints):
+        """`project_joints` for every frame, written elementwise: [B,24,3] -> [B,24,2]"""
+        H, W = self.shape
+        x, y, z = world_joints[..., 0], world_joints[..., 1], world_joints[..., 2]
+        P = self.P[:, None]                                                                        # [B,1,3,4]
+        cam = [((P[..., k, 0] * x + P[..., k, 1] * y) + P[..., k, 2] * z) + P[..., k, 3] for k in range(3)]
+        valid = (world_joints != 0).all(2) & (cam[2] > 0)
+        vf = valid.to(world_joints.dtype)
+        depth = torch.where(valid, cam[2], torch.ones_like(cam[2]))
+        u, v = cam[0] * vf / depth, cam[1] * vf / depth
+        valid = valid & (u >= 0) & (u < W - 1) & (v < H - 1)
+        return torch.stack([u, v], 2) * valid[..., None].to(u.dtype)
+
+    def terms(self, poses):
+        """-> (joint terms [B], silhouette terms [B]): frame b's are `Objective.terms` of frame b"""
+        world_verts, world_joints = self.forward_bodies(poses)
+        d = (self.project(world_joints) - self.joints_target) * self.joints_mask[..., None]
+        joint_terms = (d * d).sum(dim=(1, 2)) / self.joints_count
+        e = self.silhouette(world_verts) - self.mask_target
+        return joint_terms, (e * e).sum(dim=(1, 2)) / float(self.shape[0] * self.shape[1])
+
+    def loss(self, poses):
+        joint_terms, silhouette_terms = self.terms(poses)
+        return (joint_terms + silhouette_terms).sum()
+
+
+def optimize_smpl_sequence(caps, smpls, faces, body_model, alignments, scale, num_iters=100, sigma=1e-4, frames_per_batch=32):
+    """`optimize_smpl` for every capture of a sequence -> the refined poses, numpy [N,72] float32.  The N frames are fitted `frames_per_batch` at
+    a time: one Adam (lr 5e-3) on a [B,72] parameter per chunk under `SequenceObjective.loss`, the gradient masked per frame by
+    turn_smpl_gradient_on(cap.densepose) and clip_smpl_vals().  Adam is elementwise and every frame's gradient is its own, so a frame's result
+    is the same bits whatever the chunking (alone, or anywhere in a chunk of any size).  `alignments`: main()'s dict keyed by
+    os.path.basename(cap.image_path), or one [4,3] per capture.  All captures must share one image size (ValueError otherwise: group them).
+    Masks, keypoints, cameras and gradient masks are uploaded once per chunk; inside the loop the only host read is the silhouette's list
+    total, once per iteration."""
+    N = len(caps)
+    if len(smpls) != N:
+        raise ValueError(f"{N} captures but {len(smpls)} smpls")
+    if frames_per_batch < 1:
+        raise ValueError(f"frames_per_batch must be >= 1, got {frames_per_batch}")
+    sizes = sorted({raster.camera_of(cap)[5:] for cap in caps})
+    if len(sizes) > 1:
+        raise ValueError(f"the captures of a sequence fit must share one image size, got (W, H) = {sizes}: group them by size")
+    device = body_model.v_template.device
+    limits = torch.from_numpy(clip_smpl_vals()).float().to(device)
+    out = np.zeros((N, 72), np.float32)
+    for lo in range(0, N, frames_per_batch):
+        idx = range(lo, min(lo + frames_per_batch, N))
+        chunk = [caps[i] for i in idx]
+        aligns = [_alignment_of(alignments, caps[i], i) for i in idx]
+        objective = SequenceObjective(chunk, [smpls[i] for i in idx], faces, body_model, aligns, scale, sigma)
+        start = np.stack([np.asarray(smpls[i]['pose'], np.float32).reshape(-1) for i in idx])
+        poses = torch.nn.Parameter(torch.from_numpy(start).to(device), requires_grad=True)
+        optim = torch.optim.Adam([{"params": poses, "lr": 5e-3}])
+        grad_mask = torch.from_numpy(np.stack([turn_smpl_gradient_on(cap.densepose) for cap in chunk])).float().to(device)
+        for _ in range(num_iters):
+            optim.zero_grad()
+            objective.loss(poses).backward()
+            valid_mask = ((poses < limits[..., 1]) * (poses > limits[..., 0])).float()
+            poses.grad = poses.grad * grad_mask * valid_mask
+            optim.step()
+        out[lo:lo + len(chunk)] = poses.detach().cpu().numpy()
+    return out
+
+
+def optimize_scene(caps, smpls, faces, body_model, alignments, scale, **kw):
+    """The loop of main() (:277-293) over a scene's captures on the batched fit -> {1: {'pose': [N x [72] f32], 'betas': [N x the input
+    betas, untouched]}}, the dict main() dumps as smpl_output_optimized.pkl.  `alignments` is alignments.npy's dict, keyed by
+    os.path.basename(cap.image_path) as there; **kw go to `optimize_smpl_sequence` (num_iters, sigma, frames_per_batch).  Reading the scene
+    and WRITING THE .pkl stay with the caller: the reference dumps with joblib, which is not a dependency of this package --
+    `joblib.dump(result, path)` on the returned dict is the whole of it."""
+    poses = optimize_smpl_sequence(caps, smpls, faces, body_model, alignments, scale, **kw)
+    results = {1: {'pose': [], 'betas': []}}
+    for i in range(len(caps)):
+        results[1]['pose'].append(poses[i])
+        results[1]['betas'].append(smpls[i]['betas'])
+    return results

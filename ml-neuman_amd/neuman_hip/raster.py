@@ -134,6 +134,87 @@ class Rasterizer:
         return g_verts
 
 
+    def _batch(self, verts, cameras, who):
+        """verts [B,V,3] on the device, cameras = (w2c [B,4,4] f64, intr [B,4] f64 (fx, fy, cx, cy), W, H), both on verts' device"""
+        if not isinstance(verts, torch.Tensor) or not verts.is_cuda:
+            raise _lib.NeumanHipError("verts must be a CUDA (HIP) tensor: the rasteriser has no CPU path")
+        verts = verts.detach().to(torch.float32).contiguous()
+        w2c, intr, W, H = cameras
+        B = verts.shape[0] if verts.dim() == 3 else -1
+        if B < 1 or tuple(verts.shape) != (B, self.V, 3) or tuple(w2c.shape) != (B, 4, 4) or tuple(intr.shape) != (B, 4):
+            raise _lib.NeumanHipError(f"{who}: verts {tuple(verts.shape)} must be [B >= 1, {self.V}, 3], w2c {tuple(w2c.shape)} [B, 4, 4], intr {tuple(intr.shape)} [B, 4]")
+        if W < 1 or H < 1:
+            raise _lib.NeumanHipError(f"{who}: empty image {W} x {H}")
+        return verts, w2c.contiguous(), intr.contiguous(), B, int(W), int(H)
+
+    def silhouette_batch(self, verts, cameras, sigma=SIGMA, blur_radius=None, want_count=False):
+        """nm_raster_silhouette_batch: B frames as one call -> (alpha [B,H,W], keep [B,H,W], n_cand [B,H,W] int32 or None); frame b's are the
+        bits `silhouette` gives on frame b.  `cameras` as `batch_cameras` makes them.  One host read per call."""
+        verts, w2c, intr, B, W, H = self._batch(verts, cameras, "silhouette_batch")
+        blur_radius = default_blur_radius(sigma) if blur_radius is None else blur_radius
+        dev = verts.device
+        with torch.cuda.device(dev):
+            alpha = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+            keep = torch.empty((B, H, W), device=dev, dtype=torch.float32)
+            n_cand = torch.empty((B, H, W), device=dev, dtype=torch.int32) if want_count else None
+            _lib.check(_lib.lib().nm_raster_silhouette_batch(self._h, _lib.dev_ptr(verts), _lib.dev_ptr(w2c, torch.float64), _lib.dev_ptr(intr, torch.float64), B,
+                                                             W, H, float(sigma), float(blur_radius), _lib.dev_ptr(alpha), _lib.dev_ptr(keep),
+                                                             _lib.dev_ptr(n_cand, torch.int32), _lib.stream_ptr()), "nm_raster_silhouette_batch")
+        return alpha, keep, n_cand
+
+    def silhouette_backward_batch(self, verts, cameras, sigma, blur_radius, keep, g_alpha):
+        """nm_raster_silhouette_backward_batch: keep [B,H,W] of `silhouette_batch`, g_alpha [B,H,W] -> g_verts [B,V,3] f32; no host read"""
+        verts, w2c, intr, B, W, H = self._batch(verts, cameras, "silhouette_backward_batch")
+        keep, g_alpha = keep.detach().to(torch.float32).contiguous(), g_alpha.detach().to(torch.float32).contiguous()
+        if tuple(keep.shape) != (B, H, W) or tuple(g_alpha.shape) != (B, H, W) or keep.device != verts.device or g_alpha.device != verts.device:
+            raise _lib.NeumanHipError(f"silhouette_backward_batch: keep {tuple(keep.shape)} and g_alpha {tuple(g_alpha.shape)} must be [{B}, {H}, {W}] on {verts.device}")
+        with torch.cuda.device(verts.device):
+            g_verts = torch.empty((B, self.V, 3), device=verts.device, dtype=torch.float32)
+            _lib.check(_lib.lib().nm_raster_silhouette_backward_batch(self._h, _lib.dev_ptr(verts), _lib.dev_ptr(w2c, torch.float64),
+                                                                      _lib.dev_ptr(intr, torch.float64), B, W, H, float(sigma), float(blur_radius),
+                                                                      _lib.dev_ptr(keep), _lib.dev_ptr(g_alpha), _lib.dev_ptr(g_verts), _lib.stream_ptr()),
+                       "nm_raster_silhouette_backward_batch")
+        return g_verts
+
+
+def batch_cameras(caps, device):
+    """The cameras of captures of ONE image size as the batched entries read them: (w2c [B,4,4] f64, intr [B,4] f64 (fx, fy, cx, cy), W, H),
+    the two arrays on `device` (one upload each).  Captures of differing (W, H) raise ValueError: the caller groups them."""
+    cams = [camera_of(c) for c in caps]
+    if not cams:
+        raise ValueError("batch_cameras: no captures")
+    sizes = sorted({(c[5], c[6]) for c in cams})
+    if len(sizes) != 1:
+        raise ValueError(f"the captures of a batch must share one image size, got (W, H) = {sizes}: group them by size")
+    w2c = np.tile(np.eye(4), (len(cams), 1, 1))
+    w2c[:, :3] = np.stack([c[0] for c in cams])
+    intr = np.array([c[1:5] for c in cams], np.float64)
+    return torch.from_numpy(w2c).to(device), torch.from_numpy(intr).to(device), sizes[0][0], sizes[0][1]
+
+
+class _SilhouetteBatchFn(torch.autograd.Function):
+    """alpha [B,H,W] as a function of verts [B,V,3]: the two batched entries of csrc/silhouette.hip; keep is what the forward saved"""
+
+    @staticmethod
+    def forward(ctx, verts, rast, cameras, sigma, blur_radius):
+        alpha, keep, _ = rast.silhouette_batch(verts, cameras, sigma, blur_radius)
+        ctx.rast, ctx.cameras, ctx.sigma, ctx.blur_radius = rast, cameras, sigma, blur_radius
+        ctx.save_for_backward(verts.detach(), keep)
+        return alpha
+
+    @staticmethod
+    def backward(ctx, g_alpha):
+        verts, keep = ctx.saved_tensors
+        g = ctx.rast.silhouette_backward_batch(verts, ctx.cameras, ctx.sigma, ctx.blur_radius, keep, g_alpha)
+        return g.to(verts.dtype), None, None, None, None
+
+
+def soft_silhouette_batch(rast, verts, cameras, sigma=SIGMA, blur_radius=None):
+    """alpha [B,H,W] f32, differentiable with respect to verts [B,V,3] (a CUDA tensor); `cameras` from `batch_cameras`"""
+    rast._batch(verts, cameras, "soft_silhouette_batch")           # (refuses a CPU tensor or a wrong shape before autograd sees it)
+    return _SilhouetteBatchFn.apply(verts, rast, cameras, float(sigma), float(default_blur_radius(sigma) if blur_radius is None else blur_radius))
+
+
 class _SilhouetteFn(torch.autograd.Function):
     """alpha [H,W] of the soft silhouette as a function of verts [V,3]: the two entries of csrc/silhouette.hip.  The backward recomputes the
     candidates from verts; keep is what the forward saved (rule S5)."""

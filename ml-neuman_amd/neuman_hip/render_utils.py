@@ -1432,3 +1432,15 @@ def soft_silhouette(verts, faces, cap, sigma=1e-4, blur_radius=None):
         raise _lib.NeumanHipError("verts must be a CUDA (HIP) tensor: the silhouette has no CPU path")
     _lib.require_gpu()
     return raster.soft_silhouette(raster.rasterizer_for(faces, verts.shape[0]), verts, raster.camera_of(cap), sigma, blur_radius)
+
+
+def soft_silhouette_batch(world_verts, faces, caps, sigma=1e-4, blur_radius=None):
+    """`soft_silhouette` for the frames of a sequence as one call: world_verts [B,V,3] (a CUDA tensor), caps the B captures (one image size;
+    ValueError otherwise) or what `raster.batch_cameras` made of them -> alpha [B,H,W] f32, differentiable with respect to world_verts.
+    Frame b's alpha and gradient are `soft_silhouette`'s bits on frame b."""
+    from . import raster
+    if not isinstance(world_verts, torch.Tensor) or not world_verts.is_cuda:
+        raise _lib.NeumanHipError("world_verts must be a CUDA (HIP) tensor: the silhouette has no CPU path")
+    _lib.require_gpu()
+    cameras = caps if isinstance(caps, tuple) else raster.batch_cameras(caps, world_verts.device)
+    return raster.soft_silhouette_batch(raster.rasterizer_for(faces, world_verts.shape[1]), world_verts, cameras, sigma, blur_radius)

@@ -174,6 +174,50 @@ class _VertexForwardFn(torch.autograd.Function):
         return None, g_pose.reshape(ctx.shapes[0]), g_beta.reshape(ctx.shapes[1]), g_al.reshape(4, 4), None, None
 
 
+class _VertexForwardBatchFn(torch.autograd.Function):
+    """vertext_forward's world vertices and world joints of B frames (csrc/smpl.hip: nm_smpl_vertex_forward_batch / _backward_batch): three
+    launches forward, eight backward, whatever B is; frame b's vertices and gradients are the one-frame Function's bits."""
+
+    @staticmethod
+    def forward(ctx, owner, poses, betas, alignments, scale, da_pose):
+        h = owner._hip_handle()
+        dev = poses.device
+        V, J = owner.v_template.shape[0], len(owner.parents_list)
+        B = poses.shape[0]
+        po, be = poses.detach().reshape(B, -1).contiguous().float(), betas.detach().reshape(B, -1).contiguous().float()
+        al = alignments.detach().to(torch.float64).reshape(B, 4, 4).contiguous()
+        da = da_pose.detach().reshape(-1).contiguous().float()
+        with torch.cuda.device(dev):
+            ws = torch.empty(int(_lib.lib().nm_smpl_vertex_batch_workspace_floats(h, B)), device=dev, dtype=torch.float32)
+            world = torch.empty((B, V, 3), device=dev, dtype=torch.float32)
+            joints = torch.empty((B, J, 3), device=dev, dtype=torch.float32)
+            _lib.check(_lib.lib().nm_smpl_vertex_forward_batch(h, _lib.dev_ptr(po), _lib.dev_ptr(be), _lib.dev_ptr(al, torch.float64), float(scale),
+                                                               _lib.dev_ptr(da), B, _lib.dev_ptr(ws), _lib.dev_ptr(world), _lib.dev_ptr(joints), None,
+                                                               _lib.stream_ptr()), "nm_smpl_vertex_forward_batch")
+        ctx.owner, ctx.scale, ctx.shapes, ctx.ws = owner, float(scale), (poses.shape, betas.shape, alignments.shape), ws
+        ctx.save_for_backward(po, be, al, da)
+        ctx.set_materialize_grads(False)                             # an output nothing reads hands backward None, not zeros: a null pointer there
+        return world, joints
+
+    @staticmethod
+    def backward(ctx, g_world, g_joints):
+        po, be, al, da = ctx.saved_tensors
+        if g_world is None and g_joints is None:
+            return None, None, None, None, None, None
+        h = ctx.owner._hip_handle()
+        dev, B = po.device, po.shape[0]
+        with torch.cuda.device(dev):
+            g_pose, g_beta = torch.empty_like(po), torch.empty_like(be)
+            g_al = torch.empty((B, 4, 4), device=dev, dtype=torch.float32)
+            gw = g_world.contiguous().float() if g_world is not None else None
+            gj = g_joints.contiguous().float() if g_joints is not None else None
+            _lib.check(_lib.lib().nm_smpl_vertex_backward_batch(h, _lib.dev_ptr(po), _lib.dev_ptr(be), _lib.dev_ptr(al, torch.float64), ctx.scale,
+                                                                _lib.dev_ptr(da), B, _lib.dev_ptr(gw), _lib.dev_ptr(gj), None, _lib.dev_ptr(ctx.ws),
+                                                                _lib.dev_ptr(g_pose), _lib.dev_ptr(g_beta), _lib.dev_ptr(g_al), _lib.stream_ptr()),
+                       "nm_smpl_vertex_backward_batch")
+        return None, g_pose.reshape(ctx.shapes[0]), g_beta.reshape(ctx.shapes[1]), g_al.reshape(ctx.shapes[2]), None, None
+
+
 class SMPLDiff(torch.nn.Module):
     """HumanNeRF.vertex_forward (models/human_nerf.py:92-122) with autograd, for the trainer's pose refinement: the skinning
     chain of models/smpl.py:266-360 (shape blend, joint regression, Rodrigues, 24-joint kinematic chain, blend of the joint
@@ -287,6 +331,18 @@ class SMPLDiff(torch.nn.Module):
             world, T = _VertexForwardFn.apply(self, pose, beta, alignment, float(scale), da)
             return world[None], T[None]
         return self.vertex_forward_torch(pose, beta, alignment, scale, da_pose)
+
+    def vertex_forward_batch(self, poses, betas, alignments, scale, da_pose=None):
+        """poses [B,J*3], betas [B,NB], alignments [B,4,4] (each one's TRANSPOSE is applied), scale -> (world_verts [B,V,3], world_joints
+        [B,J,3]) as ONE autograd.Function on csrc/smpl.hip's batched kernels; differentiable in poses, betas and alignments.  The joints
+        are those of preprocess/optimize_smpl.py:105-130 (scale * align^T * A_j applied to the rest joint).  `da_pose` [1,J*3] as in
+        `vertex_forward`, one for all frames.  Float32 CUDA tensors only: the kernels have no other path."""
+        if not (poses.is_cuda and poses.dtype == torch.float32 and isinstance(scale, (int, float))):
+            raise _lib.NeumanHipError("vertex_forward_batch: poses must be a float32 CUDA (HIP) tensor and scale a number")
+        B = poses.shape[0]
+        if poses.dim() != 2 or betas.shape[0] != B or tuple(alignments.shape) != (B, 4, 4):
+            raise _lib.NeumanHipError(f"vertex_forward_batch: poses {tuple(poses.shape)}, betas {tuple(betas.shape)}, alignments {tuple(alignments.shape)}")
+        return _VertexForwardBatchFn.apply(self, poses, betas, alignments, float(scale), self.da_smpl if da_pose is None else da_pose)
 
     def vertex_forward_torch(self, pose, beta, alignment, scale, da_pose=None):
         """vertex_forward as batched tensor algebra under torch's autograd (any device, any dtype)"""
