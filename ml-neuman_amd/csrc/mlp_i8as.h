@@ -259,17 +259,33 @@ __device__ __forceinline__ void k_i8(i32x16& t, const X8& X, const uint4* ws, Ri
 }
 struct NoRing {};
 __device__ __forceinline__ void ring_copy(NoRing&, int) {}
-// NSTEPS split-bf16 k-steps over the wave's encoding rows (chunks c0 ..), accumulated into f
+// The wave's own encoding fragments of NSTEPS k-steps (chunks 2 t + g of its rows in pw), hi / lo parts.  They depend on the lane and the k-step only,
+// not on the output block: a stage reads them ONCE, in front of its first block, and every block's k_bf takes them from registers (read inside k_bf
+// they were read again per block -- the ring's barriers keep the compiler from merging the reads -- 8 times in stage 0 and in the skip).
+// pw was written by this wave's fill_pe_wave: a wave's LDS operations execute in order, and the compiler may not lift these reads over those writes.
+template <int NSTEPS>
+struct Enc {
+    uint4 h[NSTEPS], l[NSTEPS];
+};
+template <int NSTEPS>
+__device__ __forceinline__ void load_enc(Enc<NSTEPS>& E, const uint4* pw, int g, int s) {
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int t = 0; t < NSTEPS; ++t) {
+        E.h[t] = pw[(2 * t + g) * (2 * kRows) + s];
+        E.l[t] = pw[(2 * t + g) * (2 * kRows) + kRows + s];
+    }
+}
+// NSTEPS split-bf16 k-steps over the wave's encoding rows, accumulated into f
 template <int NSTEPS, bool COPY = false, class Ring = NoRing>
-__device__ __forceinline__ void k_bf(f32x16& f, const uint4* pw, int g, int s, const uint4* ws, Ring* R = nullptr, int j0 = 0) {
+__device__ __forceinline__ void k_bf(f32x16& f, const Enc<NSTEPS>& E, const uint4* ws, Ring* R = nullptr, int j0 = 0) {
 #pragma unroll
     for (int t = 0; t < NSTEPS; ++t) {
         if (COPY && (t == 1 || t == 3)) ring_copy(*R, j0 + (t >> 1));
         const uint4 wh = ws[t * kStepU4], wl = ws[t * kStepU4 + 64];
-        const uint4 xh = pw[(2 * t + g) * (2 * kRows) + s], xl = pw[(2 * t + g) * (2 * kRows) + kRows + s];
-        f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wh), as_bf16x8(xl), f, 0, 0, 0);
-        f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wl), as_bf16x8(xh), f, 0, 0, 0);
-        f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wh), as_bf16x8(xh), f, 0, 0, 0);
+        f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wh), as_bf16x8(E.l[t]), f, 0, 0, 0);
+        f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wl), as_bf16x8(E.h[t]), f, 0, 0, 0);
+        f = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wh), as_bf16x8(E.h[t]), f, 0, 0, 0);
     }
 }
 

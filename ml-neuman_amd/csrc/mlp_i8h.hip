@@ -96,13 +96,15 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_head_i8s_kernel(const Arg
             const float sxin = sx * (256.f * kappa[9]);
             f32x16 f[4];
             float m = 0.f;
+            Enc<2> E;
+            load_enc(E, pw, g, s);
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 i32x16 t;
                 const uint4* ws = ring_enter(R, 8 + b);
                 k_i8<8>(t, X, ws, R);
                 dequant16(f[b], t, sxin, bias + nm::stage_b_off(9) + 32 * b);
-                k_bf<2>(f[b], pw, g, s, ws + 8 * kStepU4);
+                k_bf<2>(f[b], E, ws + 8 * kStepU4);
                 m = max16<true>(m, f[b]);
             }
             const float M = row_max(m), inv = inv_of(M);

@@ -92,11 +92,13 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
         {
             f32x16 f[8];
             float m = 0.f;
+            Enc<4> E;
+            load_enc(E, pw, g, s);
 #pragma unroll
             for (int b = 0; b < 8; ++b) {
                 const uint4* ws = ring_enter(R, b);
                 bias16(f[b], bias + nm::stage_b_off(0) + 32 * b);
-                k_bf<4, true>(f[b], pw, g, s, ws, &R);
+                k_bf<4, true>(f[b], E, ws, &R);
                 m = max16<true>(m, f[b]);
             }
             const float M = row_max(m), inv = inv_of(M);
@@ -125,11 +127,13 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
             }
             dequant16(f[7], tp, sxin, bias + 256 * st + 32 * 7);
             if (st == 5) {
+                Enc<4> E;                                                           // (X is dead by now)
+                load_enc(E, pw, g, s);
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const uint4* ws = ring_enter(R, 48 + u);
-                    k_bf<4, true>(f[2 * u], pw, g, s, ws, &R, 0);
-                    k_bf<4, true>(f[2 * u + 1], pw, g, s, ws + 4 * kStepU4, &R, 2);
+                    k_bf<4, true>(f[2 * u], E, ws, &R, 0);
+                    k_bf<4, true>(f[2 * u + 1], E, ws + 4 * kStepU4, &R, 2);
                 }
                 m = 0.f;                                                                // (the running maximum was taken before the encodings)
 #pragma unroll
@@ -220,13 +224,15 @@ __global__ __launch_bounds__(kWaves * 64, 2) void nerf_mlp_i8s_kernel(const Args
             const float sxin = sx * (256.f * kappa[9]);
             f32x16 f[4];
             float m = 0.f;
+            Enc<2> E;
+            load_enc(E, pw, g, s);
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 i32x16 t;
                 const uint4* ws = ring_enter(R, 77 + b);
                 k_i8<8>(t, X, ws, R);
                 dequant16(f[b], t, sxin, bias + nm::stage_b_off(9) + 32 * b);
-                k_bf<2>(f[b], pw, g, s, ws + 8 * kStepU4);
+                k_bf<2>(f[b], E, ws + 8 * kStepU4);
                 m = max16<true>(m, f[b]);
             }
             const float M = row_max(m), inv = inv_of(M);
