@@ -853,6 +853,58 @@ int nm_raster_silhouette_backward_batch(nm_raster_t h, const float* verts, const
                                         nm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * isosurface -- a scalar field on a regular grid as an indexed triangle mesh (csrc/isosurface.hip).  The reference has
+ *   no such step; it is what turns a trained density into geometry (neuman_hip/mesh_extract.py).  Marching tetrahedra
+ *   on the Kuhn (Freudenthal) split of every cell: no 256-case table and no ambiguous case; the 16 cases of a
+ *   tetrahedron are built in code from rule M5.  tests/helpers/isosurface_ref.py restates the rules in numpy.
+ *     M1 grid      field f[nz][ny][nx] DEVICE f32 at the vertices of a regular grid over aabb = HOST float[6] (lo x y z,
+ *                  hi x y z); (nx-1)(ny-1)(nz-1) cells; the dims are independent, each >= 2, nx ny nz < 2^31.  Vertex
+ *                  (i, j, k) has linear index v = (k ny + j) nx + i and position p = fmaf(i, h, lo) per axis with
+ *                  h = (hi - lo) / (n - 1), every step in float32.
+ *     M2 inside    a vertex is inside iff f > level; a NaN is outside.  No NaN or Inf reaches an output.
+ *     M3 split     a cell is six tetrahedra, one per permutation (a, b, c) of the axes in lexicographic order, with
+ *                  corners v0, v0 + e_a, v0 + e_a + e_b, v0 + (1,1,1) in that order (corners 0..3).  The split is the same
+ *                  in every cell, so neighbours agree on shared faces and the surface is watertight by construction.
+ *     M4 vertices  every mesh vertex lies on one of the seven edges leaving a grid vertex toward higher indices: direction
+ *                  d = m - 1 for the offset mask m = 1..7 (bit 0 +x, bit 1 +y, bit 2 +z: x, y, xy, z, xz, yz, xyz).  Edge id
+ *                  = 7 v + d.  An edge is crossed iff its endpoints differ in M2.  The mesh vertex index is the rank of
+ *                  its edge among the crossed edges in ascending edge id (count -> scan -> fill, no atomics: the same
+ *                  bits on every run).  Position: from the lower-index endpoint a toward b, per axis,
+ *                  t = (level - fa) / (fb - fa) as an IEEE float32 division, p = fmaf(t, pb - pa, pa); where t is not
+ *                  in [0, 1] (an endpoint is NaN or infinite) t = 0.5.
+ *     M5 faces     a tetrahedron with 1 or 3 inside corners gives one triangle, on the three edges that join the lone
+ *                  corner L to the others X < Y < Z: (LX, LY, LZ).  With 2 inside corners A < B and outside C < D it gives two:
+ *                  the quad (AC, AD, BD, BC) cut along the diagonal from AC -- the edge at (lowest inside, lowest
+ *                  outside) -- to the opposite edge BD: (AC, AD, BD), (AC, BD, BC).  The last two vertices of every triangle are
+ *                  swapped iff [the corner list (inside ascending, then outside ascending) is an odd permutation of 0..3] xor
+ *                  [(a, b, c) is an odd permutation]: orientation comes from the case and the tetrahedron's parity, never
+ *                  from computed geometry, so triangles of zero area (grid values equal to level) are wound consistently too.
+ *                  Counter-clockwise vertices: the normal points from inside to outside.  Output order: cells in
+ *                  (k, j, i) order, then tetrahedron 0..5, then triangle 0..1; offsets from a scan.
+ *     M6 normals   per mesh vertex: -g / |g|, g = fmaf(t, gb - ga, ga) per axis from the gradients at the edge's endpoints
+ *                  with M4's t; gradient per axis = (f[i+1] - f[i-1]) / (2 h), at a box face (f[1] - f[0]) / h resp.
+ *                  (f[n-1] - f[n-2]) / h; |g| = sqrt((gx gx + gy gy) + gz gz).  |g| zero or not finite gives (0, 0, 0).
+ *     M7 sizes     counts are 64-bit on the device.  nm_isosurface_count reports n_verts and n_faces to the host in ONE
+ *                  16-byte read-back (a stream synchronise) and nothing else; nm_isosurface_fill reads the same 16 bytes
+ *                  back from the workspace and refuses capacities smaller than the counts.
+ *   workspace: DEVICE, 16-byte aligned, nm_isosurface_workspace_bytes(nx, ny, nz) bytes = 2.5 bytes per grid vertex (one byte of
+ *     crossed-edge flags, one byte of the anchored cell's face count, two uint16 prefix counts per eight vertices) + 32 bytes
+ *     per 2048 vertices (the scan's spans) + 64: no index is stored per edge; a vertex index is recovered by a rank query.
+ *     nm_isosurface_count fills it; nm_isosurface_fill takes it with the same field, dims and level and writes verts [n_verts,3]
+ *     f32, normals [n_verts,3] f32 (nullable) and faces [n_faces,3] int32.  A mesh of 2^31 vertices or faces or more is
+ *     counted but not filled (NM_ERR_UNSUPPORTED).  With n_verts = 0 the fill launches nothing; an output of capacity 0 may be null.
+ *   NM_ERR_ARG (with the entry's name in nm_last_error()) before any device work for a null pointer, a dim < 2 or 2^31
+ *   vertices, a box that is not finite or not lo < hi on every axis, a level that is not finite, a workspace that is
+ *   misaligned or short.
+ * ------------------------------------------------------------------------------------------- */
+int64_t nm_isosurface_workspace_bytes(int nx, int ny, int nz);
+int nm_isosurface_count(const float* field, int nx, int ny, int nz, const float* aabb, float level, void* workspace, int64_t workspace_bytes,
+                        int64_t* n_verts, int64_t* n_faces, nm_stream_t stream);
+int nm_isosurface_fill(const float* field, int nx, int ny, int nz, const float* aabb, float level, const void* workspace,
+                       int64_t workspace_bytes, float* verts, float* normals, int32_t* faces, int64_t cap_verts, int64_t cap_faces,
+                       nm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SURVEY 8f-1 (first slice): device primitives of a training step of the background NeRF --
  *   reference trainers/vanilla_nerf_trainer.py:45-96 (forward with grad) + torch autograd's backward
  *   of models/vanilla.py:120-152 and utils/render_utils.py:69-105.  The layer loop is host code
