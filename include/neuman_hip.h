@@ -905,6 +905,66 @@ int nm_isosurface_fill(const float* field, int nx, int ny, int nz, const float* 
                        nm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * mesh components -- clean-up of an indexed triangle mesh (csrc/mesh_components.hip): its connected components, their
+ *   sizes and boxes, and the mesh compacted to a chosen subset of them.  A learned density thresholded at any level is the
+ *   body plus small closed blobs in empty space; this is what drops them (neuman_hip/mesh_extract.py: components,
+ *   select_components, clean_mesh).  tests/helpers/mesh_components_ref.py restates the rules in numpy.
+ *     C1 mesh      faces [F,3] DEVICE int32 over V vertices, 0 <= V, F < 2^31 (passed as int64_t).  A face that names an
+ *                  index outside [0, V) is invalid: it is counted and never dereferenced.  With any invalid face
+ *                  nm_mesh_components returns NM_ERR_ARG, nm_last_error() gives their number and the lowest invalid face
+ *                  index, and nothing outside the caller's buffers has been written.  (The other three entry points take
+ *                  labels, so they never follow an index or a label that is out of range: such a face or vertex counts
+ *                  nowhere and is kept nowhere.)
+ *     C2 connect   two vertices are connected if some face names both (vertex connectivity: what a welded marching-
+ *                  tetrahedra mesh shares); components are the classes of that relation among the REFERENCED vertices.
+ *                  Degenerate faces ((a,a,b), (a,a,a)) and repeated faces count like any other.  A vertex that no face
+ *                  names has label -1 and belongs to no component.
+ *     C3 labels    a component's representative is its smallest vertex index; its id is the rank of the representative
+ *                  among all representatives in ascending order, 0 .. C-1.  vert_label [V] int32; face_label [F] int32
+ *                  (nullable) = the label of the face's first vertex.
+ *     C4 stats     comp_verts [C], comp_faces [C] int32; with verts [V,3] f32 given, comp_box [C,6] f32 (lo x y z, hi x y z)
+ *                  over the component's vertices in the order -inf < ... < -0 < +0 < ... < +inf; a NaN coordinate is
+ *                  skipped, an axis with no usable coordinate reads +inf, -inf.  verts == NULL requires comp_box == NULL.
+ *     C5 select    keep [C] DEVICE uint8.  A vertex is kept iff its label is >= 0 and keep[label] != 0; a face is kept iff
+ *                  its label (its first vertex's) is kept.  A kept vertex's new index is its rank among the kept vertices in
+ *                  ascending old index; kept faces stay in their old order with their indices remapped.  vert_src
+ *                  [n_verts_out] int32 (new -> old) is exactly the idx nm_gather_rows takes; faces_out [n_faces_out,3]
+ *                  int32.  Keeping everything on a mesh without unreferenced vertices reproduces it byte for byte;
+ *                  keeping nothing gives two empty outputs.
+ *     C6 reads     nm_mesh_components reports {n_components, n_invalid, first_invalid} in ONE 24-byte read-back (a stream
+ *                  synchronise); nm_mesh_select_count {n_verts_out, n_faces_out} in one of 16 bytes.
+ *                  nm_mesh_component_stats and nm_mesh_select_fill read nothing back and do not synchronise:
+ *                  nm_mesh_select_count leaves its totals in the workspace AND remembers them on the host under the
+ *                  workspace's address (the 64 most recent workspaces; any later nm_mesh_components or
+ *                  nm_mesh_select_count on that workspace replaces the record); nm_mesh_select_fill compares its counts
+ *                  with that record on the host, and its kernel with the workspace's header.
+ *     C7 determinism  every output is a function of the inputs alone, byte-identical from run to run, and vert_label
+ *                  does not change when the rows of faces are permuted: labelling is a lock-free union-find in which the
+ *                  larger root is linked under the smaller by compare-and-swap, so a class's root ends as its smallest
+ *                  vertex under every interleaving; the rankings are count -> scan -> fill.  Only integer atomics whose
+ *                  result is order-independent are used (compare-and-swap, min, max, add), the boxes through the order-
+ *                  preserving integer image of a float; nothing adds floats atomically.
+ *   workspace: DEVICE, 16-byte aligned, nm_mesh_components_workspace_bytes(V, F) bytes = 9 bytes per vertex (parent and rank,
+ *     4 bytes each, one flag byte) + 4 bytes per face (its rank) + 16 bytes per 1024 vertices and per 1024 faces (the scans'
+ *     spans) + 64 and padding below 64: linear in V and F, under 16 V + 8 F + 256.  The same size serves nm_mesh_components
+ *     and the selection pair, which may share one buffer (labels and statistics are outputs, not workspace).
+ *     nm_mesh_select_count fills it; nm_mesh_select_fill takes it with the same faces, V, F, labels and keep.
+ *   NM_ERR_ARG (with the entry's name in nm_last_error()) before any device work for a null pointer (an array of no rows may
+ *   be null), a count that is negative or >= 2^31, a workspace that is misaligned or short, comp_box without verts,
+ *   n_verts_out / n_faces_out other than what nm_mesh_select_count left for this workspace.
+ * ------------------------------------------------------------------------------------------- */
+int64_t nm_mesh_components_workspace_bytes(int64_t V, int64_t F);
+int nm_mesh_components(const int32_t* faces, int64_t F, int64_t V, int32_t* vert_label, int32_t* face_label /* nullable */, void* workspace,
+                       int64_t workspace_bytes, int64_t* n_components, nm_stream_t stream);
+int nm_mesh_component_stats(const int32_t* faces, int64_t F, int64_t V, const int32_t* vert_label, const float* verts /* nullable */, int64_t C,
+                            int32_t* comp_verts, int32_t* comp_faces, float* comp_box /* nullable */, nm_stream_t stream);
+int nm_mesh_select_count(const int32_t* faces, int64_t F, int64_t V, const int32_t* vert_label, const uint8_t* keep, int64_t C, void* workspace,
+                         int64_t workspace_bytes, int64_t* n_verts_out, int64_t* n_faces_out, nm_stream_t stream);
+int nm_mesh_select_fill(const int32_t* faces, int64_t F, int64_t V, const int32_t* vert_label, const uint8_t* keep, int64_t C,
+                        const void* workspace, int64_t workspace_bytes, int32_t* vert_src, int32_t* faces_out, int64_t n_verts_out,
+                        int64_t n_faces_out, nm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SURVEY 8f-1 (first slice): device primitives of a training step of the background NeRF --
  *   reference trainers/vanilla_nerf_trainer.py:45-96 (forward with grad) + torch autograd's backward
  *   of models/vanilla.py:120-152 and utils/render_utils.py:69-105.  The layer loop is host code

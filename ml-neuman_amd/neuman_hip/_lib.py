@@ -227,6 +227,12 @@ SIGNATURES = {
                                   ctypes.POINTER(i64), c_stream]),
     "nm_isosurface_fill": (i32, [c_f32p, i32, i32, i32, ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_void_p, i64, c_f32p, c_f32p, c_i32p,
                                  i64, i64, c_stream]),
+    "nm_mesh_components_workspace_bytes": (i64, [i64, i64]),
+    "nm_mesh_components": (i32, [c_i32p, i64, i64, c_i32p, c_i32p, ctypes.c_void_p, i64, ctypes.POINTER(i64), c_stream]),
+    "nm_mesh_component_stats": (i32, [c_i32p, i64, i64, c_i32p, c_f32p, i64, c_i32p, c_i32p, c_f32p, c_stream]),
+    "nm_mesh_select_count": (i32, [c_i32p, i64, i64, c_i32p, ctypes.c_void_p, i64, ctypes.c_void_p, i64, ctypes.POINTER(i64), ctypes.POINTER(i64),
+                                   c_stream]),
+    "nm_mesh_select_fill": (i32, [c_i32p, i64, i64, c_i32p, ctypes.c_void_p, i64, ctypes.c_void_p, i64, c_i32p, c_i32p, i64, i64, c_stream]),
 }
 
 _lib = None

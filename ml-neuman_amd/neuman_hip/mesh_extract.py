@@ -10,7 +10,14 @@ SMPL surface, save_ply to hand it on.
 
 `density_grid` samples the raw (pre-ReLU) density sigma, which is smooth through zero, on the grid of rule M1 with the density-only launch
 (nm_mlp_sigma_rays) at the precision of the net's coarse pass; `extract_mesh` runs marching tetrahedra on any such grid.  `level` has no
-default: a sensible density threshold depends on the scene's scale.  Every tensor is a CUDA tensor; there is no CPU path."""
+default: a sensible density threshold depends on the scene's scale.  Every tensor is a CUDA tensor; there is no CPU path.
+
+A learned density crosses any level in empty space too: the mesh is the body plus small closed blobs.  `components` labels the connected
+components of a mesh, `select_components` compacts it to some of them and `clean_mesh` does both (csrc/mesh_components.hip; the header's
+'mesh components', rules C1-C7); `extract_net_mesh(..., largest=, min_faces=)` cleans before it evaluates colours:
+
+    verts, faces, normals, colours = extract_net_mesh(human.coarse_human_net, box, 128, level=10.0, largest=1)      # the body alone
+    verts, faces, normals = clean_mesh(verts, faces, normals, largest=None, min_faces=200)                             # or: drop the small ones"""
 import ctypes
 import struct
 
@@ -114,12 +121,149 @@ def extract_mesh(field, aabb, level):
     return verts, faces, normals
 
 
-def extract_net_mesh(net, aabb, res, level, colour=True, precision=None, slab_bytes=SLAB_BYTES):
+class Components:
+    """What `components` returns, every tensor on the mesh's device: vert_label [V] int32 (-1: no face names the vertex), face_label [F]
+    int32, n (the number of components, a Python int), n_verts [n] and n_faces [n] int32, box [n,6] float32 (lo xyz, hi xyz) or None."""
+    __slots__ = ('vert_label', 'face_label', 'n', 'n_verts', 'n_faces', 'box')
+
+    def __init__(self, vert_label, face_label, n, n_verts, n_faces, box):
+        self.vert_label, self.face_label, self.n, self.n_verts, self.n_faces, self.box = vert_label, face_label, n, n_verts, n_faces, box
+
+
+def _mesh_faces(faces, who):
+    if not isinstance(faces, torch.Tensor) or not faces.is_cuda:
+        raise _lib.NeumanHipError(f"{who}: faces must be a CUDA (HIP) tensor: there is no CPU path")
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise _lib.NeumanHipError(f"{who}: faces must be int32 [F, 3], got {faces.dtype} {tuple(faces.shape)}")
+    return faces.detach().contiguous()
+
+
+def _vertex_rows(a, n_verts, dev, who, name):
+    if not isinstance(a, torch.Tensor) or not a.is_cuda:
+        raise _lib.NeumanHipError(f"{who}: {name} must be a CUDA (HIP) tensor: there is no CPU path")
+    if a.dim() != 2 or a.shape[0] != n_verts or a.shape[1] < 1 or a.dtype != torch.float32 or a.device != dev:
+        raise _lib.NeumanHipError(f"{who}: {name} must be float32 [{n_verts}, w] on {dev}, got {a.dtype} {tuple(a.shape)} on {a.device}")
+    return a.detach().contiguous()
+
+
+def _workspace(L, n_verts, n_faces, dev):
+    nbytes = int(L.nm_mesh_components_workspace_bytes(n_verts, n_faces))
+    if nbytes < 0:
+        _lib.check(nbytes, "nm_mesh_components_workspace_bytes")
+    return torch.empty((nbytes,), device=dev, dtype=torch.uint8), nbytes
+
+
+def components(faces, n_verts, verts=None):
+    """The connected components of the mesh faces [F,3] (CUDA int32) over n_verts vertices (rules C1-C4: two vertices are connected if a
+    face names both; ids in ascending order of the components' smallest vertex) -> Components.  verts [n_verts,3] (CUDA float32) adds the
+    components' boxes.  One read-back, for n; a face that names a vertex outside [0, n_verts) raises NeumanHipError."""
+    faces = _mesh_faces(faces, "components")
+    n_verts, n_faces = int(n_verts), int(faces.shape[0])
+    dev = faces.device
+    if verts is not None:
+        verts = _vertex_rows(verts, n_verts, dev, "components", "verts")
+        if verts.shape[1] != 3:
+            raise _lib.NeumanHipError(f"components: verts must be [V, 3], got {tuple(verts.shape)}")
+    L = _lib.lib()
+    I32 = torch.int32
+    with torch.cuda.device(dev):
+        ws, nbytes = _workspace(L, n_verts, n_faces, dev)
+        vert_label = torch.empty((n_verts,), device=dev, dtype=I32)
+        face_label = torch.empty((n_faces,), device=dev, dtype=I32)
+        n = ctypes.c_int64(0)
+        _lib.check(L.nm_mesh_components(_lib.dev_ptr(faces, I32), n_faces, n_verts, _lib.dev_ptr(vert_label, I32), _lib.dev_ptr(face_label, I32),
+                                        _lib.dev_ptr(ws, torch.uint8), nbytes, ctypes.byref(n), _lib.stream_ptr()), "nm_mesh_components")
+        C = int(n.value)
+        comp_verts = torch.empty((C,), device=dev, dtype=I32)
+        comp_faces = torch.empty((C,), device=dev, dtype=I32)
+        box = None if verts is None else torch.empty((C, 6), device=dev, dtype=torch.float32)
+        _lib.check(L.nm_mesh_component_stats(_lib.dev_ptr(faces, I32), n_faces, n_verts, _lib.dev_ptr(vert_label, I32), _lib.dev_ptr(verts), C,
+                                             _lib.dev_ptr(comp_verts, I32), _lib.dev_ptr(comp_faces, I32), _lib.dev_ptr(box), _lib.stream_ptr()),
+                   "nm_mesh_component_stats")
+    return Components(vert_label, face_label, C, comp_verts, comp_faces, box)
+
+
+def select_components(verts, faces, comps, keep, *attrs):
+    """The mesh (verts [V,3], faces [F,3]) compacted to the components of `comps` (what `components` returned for it) with keep[c] set
+    (rule C5; keep: bool or uint8 CUDA tensor [comps.n]) -> (verts', faces', *attrs'): kept vertices and faces in their old order, face
+    indices remapped; verts and every attribute (float32 [V, w], any width) gathered by nm_gather_rows.  One read-back, for the sizes."""
+    faces = _mesh_faces(faces, "select_components")
+    dev = faces.device
+    if not isinstance(verts, torch.Tensor) or not verts.is_cuda:
+        raise _lib.NeumanHipError("select_components: verts must be a CUDA (HIP) tensor: there is no CPU path")
+    n_verts, n_faces = int(verts.shape[0]), int(faces.shape[0])
+    rows = [_vertex_rows(a, n_verts, dev, "select_components", "verts" if i == 0 else f"attribute {i - 1}") for i, a in enumerate((verts,) + attrs)]
+    if not isinstance(keep, torch.Tensor) or not keep.is_cuda or keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (comps.n,):
+        raise _lib.NeumanHipError(f"select_components: keep must be a bool or uint8 CUDA tensor [{comps.n}]")
+    if tuple(comps.vert_label.shape) != (n_verts,):
+        raise _lib.NeumanHipError(f"select_components: comps labels {comps.vert_label.shape[0]} vertices, the mesh has {n_verts}")
+    keep = keep.to(torch.uint8).contiguous()
+    label = comps.vert_label.contiguous()
+    L = _lib.lib()
+    I32, U8 = torch.int32, torch.uint8
+    with torch.cuda.device(dev):
+        ws, nbytes = _workspace(L, n_verts, n_faces, dev)
+        nv, nf = ctypes.c_int64(0), ctypes.c_int64(0)
+        mesh = (_lib.dev_ptr(faces, I32), n_faces, n_verts, _lib.dev_ptr(label, I32), _lib.dev_ptr(keep, U8), comps.n, _lib.dev_ptr(ws, U8), nbytes)
+        _lib.check(L.nm_mesh_select_count(*mesh, ctypes.byref(nv), ctypes.byref(nf), _lib.stream_ptr()), "nm_mesh_select_count")
+        nv, nf = int(nv.value), int(nf.value)
+        vert_src = torch.empty((nv,), device=dev, dtype=I32)
+        faces_out = torch.empty((nf, 3), device=dev, dtype=I32)
+        _lib.check(L.nm_mesh_select_fill(*mesh, _lib.dev_ptr(vert_src, I32), _lib.dev_ptr(faces_out, I32), nv, nf, _lib.stream_ptr()),
+                   "nm_mesh_select_fill")
+        out = []
+        for a in rows:
+            g = torch.empty((nv, a.shape[1]), device=dev, dtype=torch.float32)
+            _lib.check(L.nm_gather_rows(_lib.dev_ptr(a), _lib.dev_ptr(vert_src, I32), None, nv, int(a.shape[1]), _lib.dev_ptr(g), _lib.stream_ptr()),
+                       "nm_gather_rows")
+            out.append(g)
+    return (out[0], faces_out, *out[1:])
+
+
+def _check_clean(largest, min_faces):
+    if largest is not None and (isinstance(largest, bool) or not isinstance(largest, (int, np.integer)) or largest < 1):
+        raise ValueError(f"largest must be None (no limit) or an int >= 1, got {largest!r}")
+    if isinstance(min_faces, bool) or not isinstance(min_faces, (int, np.integer)) or min_faces < 0:
+        raise ValueError(f"min_faces must be an int >= 0, got {min_faces!r}")
+
+
+def keep_mask(n_faces, largest=1, min_faces=0):
+    """clean_mesh's choice as a uint8 mask [C] from the components' face counts n_faces [C] (CUDA int32), computed on the device: the
+    components of at least min_faces faces, and among those the `largest` biggest by face count (None: all), ties to the lower id."""
+    _check_clean(largest, min_faces)
+    enough = n_faces >= int(min_faces)
+    if largest is None:
+        return enough.to(torch.uint8)
+    order = torch.sort(torch.where(enough, n_faces, torch.full_like(n_faces, -1)), descending=True, stable=True).indices
+    keep = torch.zeros_like(enough)
+    keep[order[:int(largest)]] = True
+    return (keep & enough).to(torch.uint8)
+
+
+def clean_mesh(verts, faces, *attrs, largest=1, min_faces=0):
+    """Drop the floaters: keep the components with at least min_faces faces, and among those the `largest` biggest by face count (ties to
+    the lower id; None: all of them) -> (verts', faces', *attrs') as select_components.  The default keeps the one largest component;
+    largest=None, min_faces=0 returns the input mesh as it is.  Two read-backs: the number of components and the output's sizes."""
+    _check_clean(largest, min_faces)
+    if largest is None and min_faces == 0:
+        return (verts, faces, *attrs)
+    if not isinstance(verts, torch.Tensor) or not verts.is_cuda:
+        raise _lib.NeumanHipError("clean_mesh: verts must be a CUDA (HIP) tensor: there is no CPU path")
+    comps = components(faces, verts.shape[0])
+    return select_components(verts, faces, comps, keep_mask(comps.n_faces, largest, min_faces), *attrs)
+
+
+def extract_net_mesh(net, aabb, res, level, colour=True, precision=None, slab_bytes=SLAB_BYTES, largest=None, min_faces=0):
     """density_grid + extract_mesh on a static net (a background Joiner, or HumanNeRF.coarse_human_net with the box of
     occupancy.canonical_aabb) -> (verts, faces, normals, colours).  colour: per-vertex RGB [Nv,3] in [0, 1], the sigmoid of the net's own
-    forward at the vertices seen along -normal (from outside, head on); the plain head takes no view.  Otherwise colours is None."""
+    forward at the vertices seen along -normal (from outside, head on); the plain head takes no view.  Otherwise colours is None.
+    largest / min_faces: clean_mesh's, run on (verts, faces, normals) before the colours, which are then evaluated at kept vertices only;
+    the defaults keep everything."""
+    _check_clean(largest, min_faces)
     field = density_grid(net, aabb, res, precision=precision, slab_bytes=slab_bytes)
     verts, faces, normals = extract_mesh(field, aabb, level)
+    if largest is not None or min_faces != 0:
+        verts, faces, normals = clean_mesh(verts, faces, normals, largest=largest, min_faces=min_faces)
     colours = None
     if colour:
         with torch.no_grad():
