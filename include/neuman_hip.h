@@ -965,6 +965,47 @@ int nm_mesh_select_fill(const int32_t* faces, int64_t F, int64_t V, const int32_
                         int64_t n_faces_out, nm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * mesh pose -- a canonical-space mesh animated by the body it is bound to (csrc/mesh_pose.hip): per vertex and frame the
+ *   barycentric blend of three of the body's per-vertex transforms, applied to the canonical point and normal.  It is the blend
+ *   of section a11's warp -- reference utils/ray_utils.py:56-58, `T_interp = (T[faces[f]] * bary[..., None, None]).sum(axis=1)` --
+ *   run FORWARDS: the reference inverts the blend to take an observed sample to canonical space (:58), this applies it as it is
+ *   to take a canonical vertex to the scene, for every frame of a sequence in one launch.  neuman_hip/mesh_pose.py (bind_mesh,
+ *   pose_mesh, pose_mesh_frames) binds an extracted mesh (section 'isosurface', 'mesh components') and poses it;
+ *   tests/helpers/mesh_pose_ref.py restates the rules in numpy.
+ *     P1 inputs    all pointers are DEVICE pointers.  T [B, t_rows, 4, 4] row-major canonical -> scene transforms, 16-byte aligned:
+ *                  t_f64 = 1: float64, what nm_smpl_frames writes (t_rows = V + J); t_f64 = 0: float32, what
+ *                  nm_smpl_vertex_forward_batch's T_out is (t_rows = V).  tri [N,3] int32 row indices into a frame's table,
+ *                  bary [N,3] f32; with per_frame_binding = 1 both are [B,N,3].  pts, normals [N,3] f32: the canonical mesh,
+ *                  shared by all frames.  out_pts, out_normals [B,N,3] f32.  1 <= B <= 65535 (the frame is a grid dimension, as in
+ *                  the batched SMPL entries), 0 <= N < 2^31, 1 <= t_rows < 2^31.  N = 0 returns NM_OK without a launch.  Every
+ *                  offset into [B,N,3] and [B,t_rows,16] is computed in 64 bits.
+ *     P2 blend     per vertex i and frame b, in float64 (a float32 input converts exactly), elementwise over the entries of rows
+ *                  0-2 in this association, no fused multiply-add:   M = (b0 T[t0] + b1 T[t1]) + b2 T[t2]
+ *     P3 point     p_r = ((M_r0 x + M_r1 y) + M_r2 z) + M_r3 for r = 0, 1, 2 in float64, rounded once to float32.  Row 3 of a
+ *                  transform is never read: the reference likewise takes [:, :3, 0] without dividing.
+ *     P4 normal    with normals given: A = the upper 3x3 of M; its cofactor matrix C row by row = cross(A_row1, A_row2),
+ *                  cross(A_row2, A_row0), cross(A_row0, A_row1), with cross(a, b) = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0),
+ *                  each component two products and one subtraction;  n'_r = (C_r0 n0 + C_r1 n1) + C_r2 n2;
+ *                  s = (n'0^2 + n'1^2) + n'2^2;  the output is n' / sqrt(s), rounded once to float32, and (0, 0, 0) if s is zero or
+ *                  not finite.  This is the normal the transformed faces' winding gives, reflections included.
+ *     P5 invalid   a vertex any of whose three indices lies outside [0, t_rows) is never dereferenced: its output point, and its
+ *                  output normal if present, is NaN in every frame (with per_frame_binding = 1: in the frames where its indices
+ *                  are bad), and *n_invalid (DEVICE int32, nullable, zeroed by the caller) is increased by one per such
+ *                  (frame, vertex) through an integer atomic add: the sum does not depend on order.  The entry reads nothing
+ *                  back and does not synchronise.
+ *     P6 determinism  every output element is a function of the inputs alone, the same bits from run to run, and frame b of a
+ *                  B-frame call is the same bits as a one-frame call on frame b's slice.  One thread per vertex and frame: no
+ *                  float atomics, no workspace, no hidden allocation.
+ *   NM_ERR_ARG (with the entry's name in nm_last_error()) before any device work for a null required pointer with N > 0,
+ *   out_normals without normals or the reverse, B, N or t_rows out of range, t_f64 or per_frame_binding other than 0 or 1, a T
+ *   that is not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+int nm_mesh_pose_batch(const void* T, int t_f64, int64_t t_rows, int B, const int32_t* tri, const float* bary, int per_frame_binding,
+                       const float* pts, const float* normals /* nullable */, int64_t N, float* out_pts,
+                       float* out_normals /* nullable iff normals is */, int32_t* n_invalid /* nullable, DEVICE, caller-zeroed */,
+                       nm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SURVEY 8f-1 (first slice): device primitives of a training step of the background NeRF --
  *   reference trainers/vanilla_nerf_trainer.py:45-96 (forward with grad) + torch autograd's backward
  *   of models/vanilla.py:120-152 and utils/render_utils.py:69-105.  The layer loop is host code

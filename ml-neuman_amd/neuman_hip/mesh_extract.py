@@ -17,7 +17,10 @@ components of a mesh, `select_components` compacts it to some of them and `clean
 'mesh components', rules C1-C7); `extract_net_mesh(..., largest=, min_faces=)` cleans before it evaluates colours:
 
     verts, faces, normals, colours = extract_net_mesh(human.coarse_human_net, box, 128, level=10.0, largest=1)      # the body alone
-    verts, faces, normals = clean_mesh(verts, faces, normals, largest=None, min_faces=200)                             # or: drop the small ones"""
+    verts, faces, normals = clean_mesh(verts, faces, normals, largest=None, min_faces=200)                             # or: drop the small ones
+
+The step after `clean_mesh` is neuman_hip.mesh_pose: `bind_mesh` binds the canonical mesh to the body, `pose_mesh` / `pose_mesh_frames` pose it
+for the frames of a sequence (csrc/mesh_pose.hip; the header's 'mesh pose', rules P1-P6)."""
 import ctypes
 import struct
 
