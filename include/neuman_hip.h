@@ -853,6 +853,52 @@ int nm_raster_silhouette_backward_batch(nm_raster_t h, const float* verts, const
                                         nm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * mesh frames -- the frames of an animated mesh as images, B frames in one call (csrc/raster_frames.hip).  The reference has
+ *   no such step: it is what shows the mesh that the isosurface section extracts and the mesh pose section animates, as a
+ *   preview that costs a fraction of one volume-rendered frame.  One topology (the handle's) and one image size; each frame
+ *   has its own vertices, normals and camera.  tests/helpers/raster_frames_ref.py restates F2-F5 in float64 on top of
+ *   tests/helpers/raster_ref.py.
+ *     F1 geometry    per frame, rules 1-3 of the mesh rasteriser hold unchanged, and frame b's face_id, zbuf and bary are the
+ *                    SAME BITS as nm_raster_mesh gives on frame b's vertices and camera, whatever B is and wherever b sits in
+ *                    the batch: the same projection, edge functions, coverage test, (z, face id) minimum and barycentric
+ *                    recomputation (csrc/raster_device.h has one copy of each).  These three outputs report the mesh alone:
+ *                    F4 does not touch them.
+ *     F2 colour      at a covered pixel, per channel in float32 without fused multiply-add: c = (b0' c0 + b1' c1) + b2' c2, the
+ *                    c_i the winning face's vertex colours.  colours == null is white: c = 1 exactly, not a blend of ones.
+ *     F3 light       with normals: n = normalize((b0' n0 + b1' n1) + b2' n2) on the SUPPLIED normals of the winning face's
+ *                    vertices (the handle's normal table is not read), p = (b0' v0 + b1' v1) + b2' v2, l = normalize(light - p),
+ *                    normalize(x) = x / max(|x|, 1e-6) as in rule 4; c *= 0.5 + 0.5 max(n.l, 0), n.l = (n0 l0 + n1 l1) + n2 l2.
+ *                    There is no specular term: an avatar's colours already carry the look.  Without normals c is unlit.
+ *     F4 occlusion   a covered pixel shows the mesh iff bg_z is null or z < bg_z[p] (z = zbuf[p], camera-space depth).  The
+ *                    comparison is strict: a NaN bg_z hides the mesh, +inf never does.
+ *     F5 bytes       a pixel that shows the mesh writes (uint8_t)fminf(fmaxf(c * 255, 0), 255) per channel: rule 5's truncation,
+ *                    and a NaN gives 0.  Every other pixel takes bg's bytes, or 255, 255, 255 when bg is null.
+ *     F6 launches    five launches and one memset whatever B is (vertex pass, count, scan, fill, raster + shade; the fill is
+ *                    skipped when nothing is covered), and ONE 16-byte read-back per call: the lists' total length and the
+ *                    bad-camera word, as in the batched silhouette.  List offsets are 64-bit.  A frame whose w2c or intr
+ *                    holds a non-finite entry is found on the device: it covers nothing (face_id -1, zbuf +inf, out = the
+ *                    background), and the call returns NM_ERR_ARG naming the first such frame AFTER every frame's outputs
+ *                    are written.
+ *     F7 same bits   every output is a function of the inputs alone and byte-identical from run to run: no float atomics; the
+ *                    order in which the integer atomics leave a (frame, tile) list shows in no output, since the minimum over
+ *                    (z, face id) does not depend on it.
+ *   Every array is a DEVICE pointer except light: verts [B,V,3] f32 (world); w2c [B,4,4] f64 and intr [B,4] f64 as
+ *   nm_raster_silhouette_batch reads them; colours [V,3] f32, ONE set for all frames, nullable; normals [B,V,3] f32 (world),
+ *   nullable; light HOST f64 [3] (world), given iff normals is; bg [B,H,W,3] uint8, nullable; bg_z [B,H,W] f32 (camera-space
+ *   z), nullable; out [B,H,W,3] uint8; face_id [B,H,W] int32, zbuf [B,H,W] f32 and bary [B,H,W,3] f32 each nullable.
+ *   Scratch, owned by the handle and only ever grown (apart from the one-frame passes' and the batched silhouette's; the
+ *   lists share the handle's list buffer, so calls on one handle go on one stream at a time):
+ *     per frame  16 V bytes (screen vertices) + 12 ceil(W / 16) ceil(H / 16) (counts, offsets); no per-frame face records or
+ *                boxes are kept: the raster pass reads a face through its three screen vertices
+ *     per call   4 bytes per list entry (sum over the frames' tiles of the faces whose screen box touches the tile) + 16
+ *   NM_ERR_ARG (with the entry's name in nm_last_error()) before any device work for: a null handle, verts, w2c, intr or out;
+ *   B < 1 or B > 65535; W * H = 0 or W * H > 2^30; normals without light or light without normals; a non-finite light.
+ * ------------------------------------------------------------------------------------------- */
+int nm_raster_frames(nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H, const float* colours,
+                     const float* normals, const double* light, const uint8_t* bg, const float* bg_z, uint8_t* out, int32_t* face_id,
+                     float* zbuf, float* bary, nm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * isosurface -- a scalar field on a regular grid as an indexed triangle mesh (csrc/isosurface.hip).  The reference has
  *   no such step; it is what turns a trained density into geometry (neuman_hip/mesh_extract.py).  Marching tetrahedra
  *   on the Kuhn (Freudenthal) split of every cell: no 256-case table and no ambiguous case; the 16 cases of a

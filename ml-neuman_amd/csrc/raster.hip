@@ -36,19 +36,7 @@ __global__ void raster_face_kernel(const float4* __restrict__ vscr, const int32_
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
     const float4 a = vscr[faces[3 * f]], b = vscr[faces[3 * f + 1]], c = vscr[faces[3 * f + 2]];
-    int4 bx = make_int4(1, 1, 0, 0);
-    const float area = (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x);
-    if (a.w > 0.f && b.w > 0.f && c.w > 0.f && area != 0.f) {
-        // the screen box clipped to the image, in tiles: conservative for rule 2 (a covered pixel's centre lies inside the closed box); a NaN
-        // fails the first comparison
-        float c0 = floorf(fminf(fminf(a.x, b.x), c.x)), c1 = floorf(fmaxf(fmaxf(a.x, b.x), c.x));
-        float r0 = floorf(fminf(fminf(a.y, b.y), c.y)), r1 = floorf(fmaxf(fmaxf(a.y, b.y), c.y));
-        if (c0 <= c1 && r0 <= r1 && c1 >= 0.f && r1 >= 0.f && c0 <= (float)(W - 1) && r0 <= (float)(H - 1)) {
-            c0 = fmaxf(c0, 0.f); c1 = fminf(c1, (float)(W - 1));
-            r0 = fmaxf(r0, 0.f); r1 = fminf(r1, (float)(H - 1));
-            bx = make_int4((int)c0 / kTile, (int)r0 / kTile, (int)c1 / kTile, (int)r1 / kTile);
-        }
-    }
+    const int4 bx = tile_box(a, b, c, W, H);
     box[f] = bx;
     if (bx.x > bx.z) return;
     rec[3 * f] = make_float4(a.x, a.y, b.x, b.y);
@@ -70,11 +58,6 @@ __global__ void raster_fill_kernel(const int4* __restrict__ box, int F, int TX, 
 }
 
 // ---- raster and shade -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
-    const float len = fmaxf(sqrtf((x * x + y * y) + z * z), kNormEps);
-    x /= len; y /= len; z /= len;
-}
-
 __global__ void __launch_bounds__(kBatch) raster_tile_kernel(const float4* __restrict__ rec, const int32_t* __restrict__ offset, const int32_t* __restrict__ list,
                                                             const int32_t* __restrict__ faces, const float* __restrict__ verts,
                                                             const float* __restrict__ vnrm, int W, int H, int TX, Shade sh, int32_t* __restrict__ face_id,
@@ -98,30 +81,12 @@ __global__ void __launch_bounds__(kBatch) raster_tile_kernel(const float4* __res
             s_rec[3 * lane + 2] = rec[3 * f + 2];
         }
         __syncthreads();
-        for (int j = 0; j < n; ++j) {
-            const float4 r0 = s_rec[3 * j], r1 = s_rec[3 * j + 1];
-            float w0, w1, w2;
-            edge_functions(r0, r1, px, py, w0, w1, w2);
-            const float s = (w0 + w1) + w2;
-            const bool in = (s > 0.f && w0 >= 0.f && w1 >= 0.f && w2 >= 0.f) || (s < 0.f && w0 <= 0.f && w1 <= 0.f && w2 <= 0.f);
-            if (in) {
-                const float z = s / ((w0 * r1.z + w1 * r1.w) + w2 * s_rec[3 * j + 2].x);
-                const int f = s_face[j];
-                if (z < zmin || (z == zmin && f < fmin)) { zmin = z; fmin = f; }
-            }
-        }
+        for (int j = 0; j < n; ++j) depth_test(s_rec[3 * j], s_rec[3 * j + 1], s_rec[3 * j + 2].x, px, py, s_face[j], zmin, fmin);
     }
     if (col >= W || row >= H) return;
     const int64_t p = (int64_t)row * W + col;
     float b0 = 0.f, b1 = 0.f, b2 = 0.f;
-    if (fmin >= 0) {
-        const float4 r0 = rec[3 * fmin], r1 = rec[3 * fmin + 1];
-        float w0, w1, w2;
-        edge_functions(r0, r1, px, py, w0, w1, w2);
-        const float q0 = w0 * r1.z, q1 = w1 * r1.w, q2 = w2 * rec[3 * fmin + 2].x;
-        const float q = (q0 + q1) + q2;
-        b0 = q0 / q; b1 = q1 / q; b2 = q2 / q;
-    }
+    if (fmin >= 0) winner_bary(rec[3 * fmin], rec[3 * fmin + 1], rec[3 * fmin + 2].x, px, py, b0, b1, b2);
     if (face_id) face_id[p] = fmin;
     if (zbuf) zbuf[p] = zmin;
     if (bary) { bary[3 * p] = b0; bary[3 * p + 1] = b1; bary[3 * p + 2] = b2; }
@@ -206,7 +171,7 @@ extern "C" {
 int nm_raster_destroy(nm_raster_t h) {
     if (!h) return NM_OK;
     void* bufs[] = {h->d_faces, h->d_adj_off, h->d_adj, h->d_vscr, h->d_vnrm, h->d_rec, h->d_box, h->d_tiles, h->d_list, h->d_gface, h->d_bvscr,
-                    h->d_brec, h->d_bbox, h->d_bcount, h->d_boffset, h->d_bgface};
+                    h->d_brec, h->d_bbox, h->d_bcount, h->d_boffset, h->d_bgface, h->d_fvscr, h->d_fcount, h->d_foffset};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete h;

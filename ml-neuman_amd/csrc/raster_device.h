@@ -1,5 +1,6 @@
-// What the mesh rasteriser (raster.hip) and the soft silhouette (silhouette.hip) share: the handle, the camera, the float64 vertex pass, the
-// exclusive scan of the per-tile counts and the edge functions that decide coverage.  Both files work on one nm_raster_t, so a pixel is
+// What the mesh rasteriser (raster.hip), its batched form with colour (raster_frames.hip) and the soft silhouette (silhouette.hip) share: the
+// handle, the camera, the float64 vertex pass, the exclusive scan of the per-tile counts, the edge functions that decide coverage and the
+// rasterisers' depth test.  Both files work on one nm_raster_t, so a pixel is
 // "inside" a face for the silhouette exactly when the rasteriser covers it.  Include after common.h.
 #pragma once
 #include "common.h"
@@ -92,6 +93,50 @@ __device__ __forceinline__ bool covers(float w0, float w1, float w2) {
     return (s > 0.f && w0 >= 0.f && w1 >= 0.f && w2 >= 0.f) || (s < 0.f && w0 <= 0.f && w1 <= 0.f && w2 <= 0.f);
 }
 
+// rule 2's rejection and the 16 x 16-pixel tiles a face can cover: (tx0, ty0, tx1, ty1), tx0 > tx1 for a face that covers nothing.  a, b, c
+// are its screen vertices (u, v, 1/z, z).  The screen box clipped to the image is conservative for rule 2 (a covered pixel's centre lies
+// inside the closed box); a NaN fails the first comparison
+__device__ __forceinline__ int4 tile_box(const float4 a, const float4 b, const float4 c, int W, int H) {
+    int4 bx = make_int4(1, 1, 0, 0);
+    const float area = (b.x - a.x) * (c.y - a.y) - (b.y - a.y) * (c.x - a.x);
+    if (a.w > 0.f && b.w > 0.f && c.w > 0.f && area != 0.f) {
+        float c0 = floorf(fminf(fminf(a.x, b.x), c.x)), c1 = floorf(fmaxf(fmaxf(a.x, b.x), c.x));
+        float r0 = floorf(fminf(fminf(a.y, b.y), c.y)), r1 = floorf(fmaxf(fmaxf(a.y, b.y), c.y));
+        if (c0 <= c1 && r0 <= r1 && c1 >= 0.f && r1 >= 0.f && c0 <= (float)(W - 1) && r0 <= (float)(H - 1)) {
+            c0 = fmaxf(c0, 0.f); c1 = fminf(c1, (float)(W - 1));
+            r0 = fmaxf(r0, 0.f); r1 = fminf(r1, (float)(H - 1));
+            bx = make_int4((int)c0 / kTile, (int)r0 / kTile, (int)c1 / kTile, (int)r1 / kTile);
+        }
+    }
+    return bx;
+}
+
+// rules 2 and 3 for one face and one pixel centre: r0 = (x0, y0, x1, y1), r1 = (x2, y2, 1/z0, 1/z1), iz2 = 1/z2.  Where the face covers the
+// pixel, its perspective-correct depth enters the pixel's (z, face id) minimum
+__device__ __forceinline__ void depth_test(const float4 r0, const float4 r1, float iz2, float px, float py, int f, float& zmin, int& fmin) {
+    float w0, w1, w2;
+    edge_functions(r0, r1, px, py, w0, w1, w2);
+    if (!covers(w0, w1, w2)) return;
+    const float s = (w0 + w1) + w2;
+    const float z = s / ((w0 * r1.z + w1 * r1.w) + w2 * iz2);
+    if (z < zmin || (z == zmin && f < fmin)) { zmin = z; fmin = f; }
+}
+
+// rule 3's b' of the winning face at the pixel centre
+__device__ __forceinline__ void winner_bary(const float4 r0, const float4 r1, float iz2, float px, float py, float& b0, float& b1, float& b2) {
+    float w0, w1, w2;
+    edge_functions(r0, r1, px, py, w0, w1, w2);
+    const float q0 = w0 * r1.z, q1 = w1 * r1.w, q2 = w2 * iz2;
+    const float q = (q0 + q1) + q2;
+    b0 = q0 / q; b1 = q1 / q; b2 = q2 / q;
+}
+
+// x / max(|x|, kNormEps)
+__device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
+    const float len = fmaxf(sqrtf((x * x + y * y) + z * z), kNormEps);
+    x /= len; y /= len; z /= len;
+}
+
 }  // namespace nm_rast
 
 struct nm_raster_s {
@@ -118,6 +163,12 @@ struct nm_raster_s {
     int64_t* d_boffset;      // [B*T+1] | {total, first bad frame + 1}: 64-bit, a batch's lists can pass 2^31 entries
     int gface_cap;           // frames d_bgface holds
     float* d_bgface;         // [B,F,3,2]: made by the first batched backward call
+    // nm_raster_frames' scratch (raster_frames.hip), apart from both of the above: grown to the largest batch / image seen
+    int frames_cap;          // frames d_fvscr holds
+    float4* d_fvscr;         // [B,V]
+    int64_t ftiles_cap;      // B * T entries
+    int32_t* d_fcount;       // [B*T] the count pass's counts, then the fill pass's cursors
+    int64_t* d_foffset;      // [B*T+1] | {total, first bad frame + 1}
 };
 
 namespace nm_rast {

@@ -7,7 +7,7 @@ utils/ray_utils.py:48-66) run forwards -- closest body triangle, barycentric ble
     verts, faces, normals = clean_mesh(*extract_mesh(field, box, level))                # canonical space
     binding = bind_mesh(verts, static_verts, body.faces)                                 # once: closest triangle + barycentrics
     posed, posed_normals = pose_mesh_frames(body, poses, betas, alignments, scale, verts, binding, normals)      # [B,N,3] each
-    frame = render_utils.rasterize_mesh(posed[b], faces, cap)                            # the faces do not change
+    frames = render_utils.render_mesh_frames(posed, faces, caps, colours, posed_normals) # uint8 [B,H,W,3]; the faces do not change
 
 The forward map takes the closest point on the CANONICAL body, the renderers' inverse map the closest point on the POSED body: the two agree
 to first order near the surface (`Binding.sdist` says how far from it a vertex sits).  Every tensor is a CUDA tensor; there is no CPU path."""

@@ -5,7 +5,10 @@ The camera of a capture is read here too: intrinsics from `cap.pinhole_cam` (the
 (synthetic.SimpleCapture), the world-to-camera matrix from `cap.cam_pose` in float64.
 
 The soft silhouette (csrc/silhouette.hip, the header's 'soft silhouette') works on the same handle: `Rasterizer.silhouette` and
-`silhouette_backward` are the two entries, `soft_silhouette` joins them under torch's autograd."""
+`silhouette_backward` are the two entries, `soft_silhouette` joins them under torch's autograd.
+
+`Rasterizer.render_frames` (csrc/raster_frames.hip, the header's 'mesh frames') renders B frames of the mesh as uint8 images in one call:
+the rasteriser's geometry per frame, per-vertex colours, a diffuse light on supplied normals, a depth test against a background."""
 import collections
 import ctypes
 import math
@@ -175,6 +178,46 @@ class Rasterizer:
                                                                       _lib.dev_ptr(keep), _lib.dev_ptr(g_alpha), _lib.dev_ptr(g_verts), _lib.stream_ptr()),
                        "nm_raster_silhouette_backward_batch")
         return g_verts
+
+    def render_frames(self, verts, cameras, colours=None, normals=None, light=LIGHT, background=None, background_z=None, want_geometry=False, out=None):
+        """nm_raster_frames (the header's 'mesh frames', rules F1-F7): B frames of the mesh as images, one call and one host read -> out uint8
+        [B,H,W,3], or (out, face_id [B,H,W] int32, zbuf [B,H,W] f32, bary [B,H,W,3] f32) with want_geometry; frame b's geometry is the bits
+        `rasterize` gives on frame b.  verts [B,V,3]; `cameras` as `batch_cameras` makes them; colours [V,3] f32 (None: white); normals
+        [B,V,3] f32 switch the diffuse light at `light` on; background uint8 [B,H,W,3] (None: white); background_z f32 [B,H,W], camera-space
+        depth the mesh must be nearer than.  `out`: a dense uint8 [B,H,W,3] tensor on verts' device to write into instead of a new one."""
+        who = "render_frames"
+        verts, w2c, intr, B, W, H = self._batch(verts, cameras, who)
+        dev = verts.device
+
+        def dense(t, name, dtype, shape):
+            if t is None:
+                return None
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise _lib.NeumanHipError(f"{who}: {name} must be a CUDA (HIP) tensor: there is no CPU path")
+            if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
+                raise _lib.NeumanHipError(f"{who}: {name} must be {dtype} {list(shape)} on {dev}, got {t.dtype} {list(t.shape)} on {t.device}")
+            return t.detach().contiguous()
+
+        colours = dense(colours, "colours", torch.float32, (self.V, 3))
+        normals = dense(normals, "normals", torch.float32, (B, self.V, 3))
+        background = dense(background, "background", torch.uint8, (B, H, W, 3))
+        background_z = dense(background_z, "background_z", torch.float32, (B, H, W))
+        if out is not None:
+            dense(out, "out", torch.uint8, (B, H, W, 3))
+            if not out.is_contiguous():
+                raise _lib.NeumanHipError(f"{who}: out must be contiguous")
+        light_p = _f64(light)[1] if normals is not None else None
+        with torch.cuda.device(dev):
+            if out is None:
+                out = torch.empty((B, H, W, 3), device=dev, dtype=torch.uint8)
+            face_id = torch.empty((B, H, W), device=dev, dtype=torch.int32) if want_geometry else None
+            zbuf = torch.empty((B, H, W), device=dev, dtype=torch.float32) if want_geometry else None
+            bary = torch.empty((B, H, W, 3), device=dev, dtype=torch.float32) if want_geometry else None
+            _lib.check(_lib.lib().nm_raster_frames(self._h, _lib.dev_ptr(verts), _lib.dev_ptr(w2c, torch.float64), _lib.dev_ptr(intr, torch.float64), B, W, H,
+                                                   _lib.dev_ptr(colours), _lib.dev_ptr(normals), light_p, _lib.dev_ptr(background, torch.uint8),
+                                                   _lib.dev_ptr(background_z), _lib.dev_ptr(out, torch.uint8), _lib.dev_ptr(face_id, torch.int32),
+                                                   _lib.dev_ptr(zbuf), _lib.dev_ptr(bary), _lib.stream_ptr()), "nm_raster_frames")
+        return (out, face_id, zbuf, bary) if want_geometry else out
 
 
 def batch_cameras(caps, device):

@@ -1444,3 +1444,90 @@ def soft_silhouette_batch(world_verts, faces, caps, sigma=1e-4, blur_radius=None
     _lib.require_gpu()
     cameras = caps if isinstance(caps, tuple) else raster.batch_cameras(caps, world_verts.device)
     return raster.soft_silhouette_batch(raster.rasterizer_for(faces, world_verts.shape[1]), world_verts, cameras, sigma, blur_radius)
+
+
+# ------------------------------------------------------------------------------------------------
+# the frames of an animated mesh (csrc/raster_frames.hip; the header's 'mesh frames', rules F1-F7): what mesh_extract made and mesh_pose posed,
+# as images
+# ------------------------------------------------------------------------------------------------
+MESH_FRAMES_SCRATCH = 256 << 20                                # bytes of scratch render_mesh_frames' default chunk aims at
+
+
+def mesh_frames_per_call(V, F, W, H, budget=MESH_FRAMES_SCRATCH):
+    """The frames one nm_raster_frames call takes under `budget` bytes of the scratch the header states: 16 V + 12 ceil(W / 16) ceil(H / 16)
+    per frame and 4 per list entry -- two entries per face assumed, which is what a mesh of faces smaller than a tile makes (a face enters
+    the list of every tile its screen box touches); at least 1, at most the entry's 65535."""
+    tiles = ((W + 15) // 16) * ((H + 15) // 16)
+    return int(max(1, min(65535, budget // (16 * V + 12 * tiles + 8 * F))))
+
+
+def depth_to_camera_z(depth, cap):
+    """A renderer's depth map of `cap` (float32 [H,W] tensor: distances along the pixels' rays) -> camera-space z [H,W], what
+    `render_mesh_frames` compares the mesh's depth with (rule F4): the distance times the component of the renderer's own unit ray
+    direction (`_all_rays`) along the camera's optical axis."""
+    from . import raster
+    h, w = cap.shape
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or tuple(depth.shape) != (h, w):
+        raise _lib.NeumanHipError(f"depth_to_camera_z: depth must be a float32 [{h}, {w}] tensor, got {getattr(depth, 'dtype', type(depth))} "
+                                  f"{tuple(getattr(depth, 'shape', ()))}")
+    d = _all_rays(cap, depth.device)[1]
+    axis = torch.as_tensor(raster.camera_of(cap)[0][2, :3]).to(depth.device, torch.float32)      # the third row of R_w2c: the optical axis in world space
+    return depth * (d @ axis).reshape(h, w)
+
+
+def render_mesh_frames(world_verts, faces, caps, colours=None, normals=None, background=None, background_depth=None, light=None, frames_per_call=None):
+    """The frames of a posed mesh as images -> uint8 [B,H,W,3] on the device.  world_verts [B,V,3] and normals [B,V,3] (optional: they switch
+    the diffuse light on) as `mesh_pose.pose_mesh_frames` returns them, faces [F,3], colours [V,3] float32 as `mesh_extract.extract_net_mesh`
+    returns them (None: white); caps the B captures (one image size; ValueError otherwise) or what `raster.batch_cameras` made of them.
+    background uint8 [B,H,W,3], or [H,W,3] for all frames (None: white); background_depth float32 [B,H,W], the renderers' depth maps of the
+    same captures: the mesh shows where it is nearer (`depth_to_camera_z` makes the comparison a camera-space one; it needs the captures
+    themselves).  light: the world-space position of the point light, `raster.LIGHT` by default.  Every tensor is a CUDA tensor on one
+    device and is taken as it is: nothing is converted.  The sequence goes through nm_raster_frames `frames_per_call` frames at a time
+    (default: `mesh_frames_per_call`), every call writing its frames straight into the result, which does not depend on the chunking."""
+    from . import raster
+    who = "render_mesh_frames"
+
+    def dense(t, name, dtype, shapes):
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.NeumanHipError(f"{who}: {name} must be a CUDA (HIP) tensor: there is no CPU path")
+        if t.dtype != dtype or tuple(t.shape) not in shapes or t.device != dev:
+            raise _lib.NeumanHipError(f"{who}: {name} must be {dtype} {' or '.join(str(list(s)) for s in shapes)} on {dev}, got {t.dtype} {list(t.shape)} "
+                                      f"on {t.device}")
+        return t.detach().contiguous()
+
+    if not isinstance(world_verts, torch.Tensor) or not world_verts.is_cuda:
+        raise _lib.NeumanHipError(f"{who}: world_verts must be a CUDA (HIP) tensor: there is no CPU path")
+    dev = world_verts.device
+    if world_verts.dim() != 3 or world_verts.shape[0] < 1 or world_verts.shape[2] != 3 or world_verts.dtype != torch.float32:
+        raise _lib.NeumanHipError(f"{who}: world_verts must be float32 [B >= 1, V, 3], got {world_verts.dtype} {list(world_verts.shape)}")
+    world_verts = world_verts.detach().contiguous()
+    B, V = int(world_verts.shape[0]), int(world_verts.shape[1])
+    cameras = caps if isinstance(caps, tuple) else raster.batch_cameras(caps, dev)
+    w2c, intr, W, H = cameras
+    if tuple(w2c.shape) != (B, 4, 4) or tuple(intr.shape) != (B, 4):
+        raise _lib.NeumanHipError(f"{who}: {w2c.shape[0]} cameras for {B} frames")
+    colours = dense(colours, "colours", torch.float32, [(V, 3)])
+    normals = dense(normals, "normals", torch.float32, [(B, V, 3)])
+    background = dense(background, "background", torch.uint8, [(B, H, W, 3), (H, W, 3)])
+    background_depth = dense(background_depth, "background_depth", torch.float32, [(B, H, W)])
+    if background_depth is not None and isinstance(caps, tuple):
+        raise _lib.NeumanHipError(f"{who}: background_depth needs the captures themselves, not their batch_cameras: the depth maps' rays come from them")
+    _lib.require_gpu()
+    step = mesh_frames_per_call(V, len(faces), W, H) if frames_per_call is None else int(frames_per_call)
+    if step < 1:
+        raise _lib.NeumanHipError(f"{who}: frames_per_call = {step}")
+    step = min(step, B, 65535)
+    rast = raster.rasterizer_for(faces, V)
+    light = raster.LIGHT if light is None else light
+    with torch.no_grad(), torch.cuda.device(dev):
+        out = torch.empty((B, H, W, 3), device=dev, dtype=torch.uint8)
+        shared = background.expand(step, H, W, 3).contiguous() if background is not None and background.dim() == 3 else None
+        for b0 in range(0, B, step):
+            b1 = min(b0 + step, B)
+            bg = None if background is None else (shared[:b1 - b0] if shared is not None else background[b0:b1])
+            bg_z = None if background_depth is None else torch.stack([depth_to_camera_z(background_depth[b], caps[b]) for b in range(b0, b1)])
+            rast.render_frames(world_verts[b0:b1], (w2c[b0:b1], intr[b0:b1], W, H), colours, None if normals is None else normals[b0:b1], light, bg, bg_z,
+                               out=out[b0:b1])
+    return out
