@@ -1052,6 +1052,74 @@ int nm_mesh_pose_batch(const void* T, int t_f64, int64_t t_rows, int B, const in
                        nm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * mesh smooth -- topology-preserving smoothing of an indexed triangle mesh (csrc/mesh_smooth.hip): the vertex -> incident
+ *   faces adjacency, Taubin lambda|mu steps over it, and vertex normals from the mesh's own faces.  A learned density is
+ *   noisy: what section 'isosurface' extracts is rippled at the scale of a grid cell.  The smoothing moves vertices only, so
+ *   `faces` stays byte for byte and every later stage ('mesh components', 'mesh pose', the rasteriser) takes the result
+ *   unchanged; the normals serve any mesh whose vertices have moved, a posed frame included (neuman_hip/mesh_smooth.py:
+ *   adjacency, smooth_mesh, vertex_normals).  tests/helpers/mesh_smooth_ref.py restates the rules in numpy.
+ *   Every product, sum and quotient below is a float64 operation rounded on its own, in the association stated, no fused
+ *   multiply-add; a float32 input converts exactly.
+ *     S1 mesh      faces [F,3] DEVICE int32 over V vertices, sizes passed as int64_t, 0 <= V < 2^31, 0 <= 3 F < 2^31.  A face
+ *                  that names an index outside [0, V) is invalid: it is counted and never dereferenced.  With any invalid face
+ *                  nm_mesh_adjacency returns NM_ERR_ARG, nm_last_error() gives their number and the lowest invalid face index
+ *                  (rule C1's behaviour), and nothing outside the caller's buffers has been written.  A valid face is PROPER
+ *                  if its three indices are pairwise distinct; only proper faces enter the adjacency: a degenerate face joins
+ *                  no list and contributes to nothing.  Repeated faces count as often as they occur.
+ *     S2 adjacency inc_off [V+1] int32, inc [3 F] int32 (allocated at the bound; the first n_incident = 3 x the number of
+ *                  proper faces entries are written).  inc[inc_off[v] .. inc_off[v+1]) holds the proper faces that name v in
+ *                  ascending face index; a vertex no proper face names has an empty list.  boundary [V] uint8 (nullable):
+ *                  boundary[v] = 1 iff there is a vertex u such that exactly one proper face names both u and v (an edge
+ *                  with one face; an edge with three or more is no boundary), else 0.  nm_mesh_adjacency reports
+ *                  {n_incident, n_invalid, first_invalid} in ONE 24-byte read-back (a stream synchronise) and nothing else.
+ *                  The lists are built count -> scan -> fill through an integer atomic cursor -> a sort of every vertex's
+ *                  segment in place by its lane: insertion sort up to 32 entries, heap sort (O(k log k), no second buffer)
+ *                  beyond, so no vertex costs time quadratic in its valence past that threshold.  The boundary flag comes from
+ *                  the sorted neighbour ids of the vertex's faces (two per face): an id that occurs exactly once.
+ *     S3 step      rows x [V,w] float32, 1 <= w <= 64 (positions: w = 3; colours or any attribute go through the same call),
+ *                  factor t.  For a vertex v with k = inc_off[v+1] - inc_off[v] > 0 and hold[v] == 0 (hold [V] uint8,
+ *                  nullable = all zero), per column:  s = 0;  for each incident face in list order, rotated so that v comes
+ *                  first, (v, p, q):  s = (s + x[p]) + x[q];  m = s / (2 k);  d = m - x[v];  x'[v] = (float)(x[v] + t d).
+ *                  This is the umbrella operator with each neighbour weighted by the faces it shares with v (on a closed
+ *                  manifold the uniform umbrella).  The sum is left to right as written: one lane's loop, never a tree.  A
+ *                  vertex with k = 0 or hold[v] != 0 keeps its bits.  A step reads only the previous step's rows (Jacobi).
+ *     S4 schedule  iterations = n >= 0; an iteration is a step with lambda, then a step with mu if mu != 0 (mu == 0: plain
+ *                  Laplacian smoothing).  All steps run in one call, ping-ponging between out and the caller's scratch (both
+ *                  [V,w]); the buffer the first step writes is chosen by parity so that the last step writes out.  n = 0
+ *                  copies rows to out byte for byte.  No read-back, no synchronise.  Taubin's pair lambda = 0.5, mu = -0.53
+ *                  has the pass-band 1/lambda + 1/mu ~ 0.11 and does not shrink the body.
+ *     S5 normals   verts [B,V,3] float32, B >= 1, B V < 2^31, the frame a grid dimension: all B frames in one launch.  For
+ *                  frame b and vertex v:  n = 0;  for each incident face f = (a, b, c) in list order and in STORED vertex order,
+ *                  u = x[b] - x[a], w = x[c] - x[a]:  n += cross(u, w) component-wise, cross(u, w) = (u1 w2 - u2 w1,
+ *                  u2 w0 - u0 w2, u0 w1 - u1 w0), each component two products and one difference;  l2 = (nx nx + ny ny) + nz nz;
+ *                  normals[b,v] = (float)(n / sqrt(l2)), and (0, 0, 0) if l2 is not finite or not > 0 or the list is empty.
+ *                  Area-weighted; outward for the counter-clockwise faces nm_isosurface_fill makes.  Frame b of a B-frame call
+ *                  is the same bits as a one-frame call on frame b.  No read-back.
+ *     S6 determinism  every output is a function of the inputs alone, byte-identical from run to run, and boundary does not
+ *                  change when the rows of faces are permuted.  Only integer atomics whose result is order-independent are used
+ *                  (add); the one order-dependent intermediate, a list's order after the fill, is removed by the sort.  Nothing
+ *                  adds floats atomically.
+ *   nm_mesh_smooth and nm_mesh_vertex_normals trust inc_off / inc only as far as nm_mesh_adjacency made them for the same
+ *   faces, V, F; they still never follow an offset, a face index or a vertex index that is out of range, nor a face that does
+ *   not name the vertex (smooth): such an entry is skipped, and a vertex none of whose entries is followed keeps its bits.
+ *   workspace: DEVICE, 16-byte aligned, nm_mesh_adjacency_workspace_bytes(V, F) bytes = 4 bytes per vertex (its counter, then
+ *     the fill's cursor) + 24 bytes per face (six neighbour ids) + 16 bytes per 1024 vertices (the scan's spans) + 64 and
+ *     padding below 32: linear in V and F, under 8 V + 24 F + 256.
+ *   NM_ERR_ARG (with the entry's name in nm_last_error()) before any device work for a null pointer (an array of no rows may
+ *   be null; inc_off never has no rows), V or 3 F negative or >= 2^31, B < 1 or B V >= 2^31, width outside 1..64,
+ *   iterations < 0, lambda or mu not finite, a workspace that is misaligned or short, rows / out / scratch (or verts /
+ *   normals) that overlap.
+ * ------------------------------------------------------------------------------------------- */
+int64_t nm_mesh_adjacency_workspace_bytes(int64_t V, int64_t F);
+int nm_mesh_adjacency(const int32_t* faces, int64_t F, int64_t V, int32_t* inc_off, int32_t* inc, uint8_t* boundary /* nullable */,
+                      void* workspace, int64_t workspace_bytes, int64_t* n_incident, nm_stream_t stream);
+int nm_mesh_smooth(const float* rows, int width, int64_t V, const int32_t* faces, int64_t F, const int32_t* inc_off, const int32_t* inc,
+                   const uint8_t* hold /* nullable */, float lambda, float mu, int iterations, float* out, float* scratch,
+                   nm_stream_t stream);
+int nm_mesh_vertex_normals(const float* verts, int64_t B, int64_t V, const int32_t* faces, int64_t F, const int32_t* inc_off,
+                           const int32_t* inc, float* normals, nm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SURVEY 8f-1 (first slice): device primitives of a training step of the background NeRF --
  *   reference trainers/vanilla_nerf_trainer.py:45-96 (forward with grad) + torch autograd's backward
  *   of models/vanilla.py:120-152 and utils/render_utils.py:69-105.  The layer loop is host code

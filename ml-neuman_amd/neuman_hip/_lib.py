@@ -236,6 +236,11 @@ SIGNATURES = {
                                    c_stream]),
     "nm_mesh_select_fill": (i32, [c_i32p, i64, i64, c_i32p, ctypes.c_void_p, i64, ctypes.c_void_p, i64, c_i32p, c_i32p, i64, i64, c_stream]),
     "nm_mesh_pose_batch": (i32, [ctypes.c_void_p, i32, i64, i32, c_i32p, c_f32p, i32, c_f32p, c_f32p, i64, c_f32p, c_f32p, c_i32p, c_stream]),
+    "nm_mesh_adjacency_workspace_bytes": (i64, [i64, i64]),
+    "nm_mesh_adjacency": (i32, [c_i32p, i64, i64, c_i32p, c_i32p, ctypes.c_void_p, ctypes.c_void_p, i64, ctypes.POINTER(i64), c_stream]),
+    "nm_mesh_smooth": (i32, [c_f32p, i32, i64, c_i32p, i64, c_i32p, c_i32p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float, i32, c_f32p, c_f32p,
+                             c_stream]),
+    "nm_mesh_vertex_normals": (i32, [c_f32p, i64, i64, c_i32p, i64, c_i32p, c_i32p, c_f32p, c_stream]),
 }
 
 _lib = None
