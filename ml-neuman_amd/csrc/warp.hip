@@ -110,13 +110,36 @@ __device__ __forceinline__ uint32_t spread10(uint32_t x) {      // 10 bits -> ev
     return x;
 }
 
-// triangle records in the caller's order + sort keys (Morton code of the centroid << 32 | face id: all distinct)
+// triangle records (face f at rec[f]; the corners in an order of the record's own, below) + sort keys (Morton code of the centroid << 32 | face id: all distinct)
 __global__ __launch_bounds__(256) void tri_prep_kernel(const float* __restrict__ verts, const int32_t* __restrict__ faces, int F,
                                                        const float* __restrict__ bbox, TriRec* __restrict__ rec,
                                                        unsigned long long* __restrict__ keys) {
     const int f = blockIdx.x * blockDim.x + threadIdx.x;
     if (f >= F) return;
-    const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+    int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
+    {
+        // A sliver whose FIRST corner holds the small angle (sin^2 < 1e-3, under 1.8 degrees) is recorded from the corner opposite its longest
+        // edge instead.  exact_tri's interior foot is (vb, vc) / |ab x ac|^2, and vb, vc are differences of products of size |ab| |ac| |ap|^2:
+        // with ab nearly parallel to ac their float32 rounding is ~1e-7 / sin^2 of the edge -- 0.5 % of a 0.36 long side of a 1e-3 thick slab,
+        // a foot 1.7e-3 off and a distance 8e-5 off (tests/test_hip_sharp_shapes.py, thin_plate).  From the well-conditioned corner the same
+        // arithmetic is accurate to rounding.  The closest point does not depend on which corner the record starts at, face ids stay the
+        // caller's.
+        const float e1x = verts[i1 * 3] - verts[i0 * 3], e1y = verts[i1 * 3 + 1] - verts[i0 * 3 + 1], e1z = verts[i1 * 3 + 2] - verts[i0 * 3 + 2];
+        const float e2x = verts[i2 * 3] - verts[i0 * 3], e2y = verts[i2 * 3 + 1] - verts[i0 * 3 + 1], e2z = verts[i2 * 3 + 2] - verts[i0 * 3 + 2];
+        const float l1 = fmaf(e1z, e1z, fmaf(e1y, e1y, e1x * e1x)), l2 = fmaf(e2z, e2z, fmaf(e2y, e2y, e2x * e2x));
+        const float l12 = fmaf(e1z, e2z, fmaf(e1y, e2y, e1x * e2x));
+        if (l1 * l2 - l12 * l12 < 1e-3f * (l1 * l2)) {
+            const float l_bc = l1 - 2.f * l12 + l2;
+            const int j0 = i0, j1 = i1, j2 = i2;
+            if (l1 > l_bc && (l1 > l2 || (l1 == l2 && j2 < j1))) { i0 = j2; i1 = j0; i2 = j1; }          // ab is the longest edge: start at c
+            else if (l2 > l_bc && (l2 > l1 || (l1 == l2 && j1 < j2))) { i0 = j1; i1 = j2; i2 = j0; }     // ac is: start at b
+        }
+    }
+    // The other two corners in the order of their vertex ids: a face and the same face with the opposite orientation share one record, so
+    // distance, face and closest point do not depend on the orientation, bit for bit, and nm_signed_distance of a reversed mesh is the exact
+    // negative (exact_tri's foot, fmaf(ac, w, fmaf(ab, v, a)), is not symmetric in (ab, v) <-> (ac, w): recorded as listed, a reversed face
+    // moved feet by an ulp and handed near-ties to the other face).
+    if (i2 < i1) { const int s = i1; i1 = i2; i2 = s; }
     const float ax = verts[i0 * 3], ay = verts[i0 * 3 + 1], az = verts[i0 * 3 + 2];
     const float bx = verts[i1 * 3], by = verts[i1 * 3 + 1], bz = verts[i1 * 3 + 2];
     const float cx = verts[i2 * 3], cy = verts[i2 * 3 + 1], cz = verts[i2 * 3 + 2];
