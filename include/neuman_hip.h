@@ -1120,6 +1120,96 @@ int nm_mesh_vertex_normals(const float* verts, int64_t B, int64_t V, const int32
                            const int32_t* inc, float* normals, nm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * mesh simplify -- an indexed triangle mesh thinned by vertex clustering on a uniform grid (csrc/mesh_simplify.hip), in the
+ *   style of Rossignac-Borrel: all vertices of a grid cell become one, and a face survives if its corners fall into three
+ *   different cells.  The cell's vertex is placed at the minimiser of the area^2-weighted plane quadrics of the faces around
+ *   the cell's members (Lindstrom's out-of-core simplification), which keeps sharp edges and corners where a mean rounds
+ *   them off; it falls back to the members' mean.  What section 'isosurface' extracts has the size its grid dictates, not the
+ *   size binding, posing and drawing a sequence need (neuman_hip/mesh_simplify.py: simplify_mesh).
+ *   tests/helpers/mesh_simplify_ref.py restates the rules in numpy.
+ *   Every product, sum and quotient below is a float64 operation rounded on its own, in the association stated, no fused
+ *   multiply-add; a float32 input converts exactly.
+ *     Q1 mesh      as S1: faces [F,3] DEVICE int32 over V vertices, sizes passed as int64_t, 0 <= V < 2^31, 0 <= 3 F < 2^31.  A
+ *                  face that names an index outside [0, V) is invalid: it is counted and never dereferenced.  With any invalid
+ *                  face nm_mesh_simplify_count returns NM_ERR_ARG, nm_last_error() gives their number and the lowest invalid
+ *                  face index, and nothing outside the caller's buffers has been written (vert_cluster is then unspecified).
+ *                  A valid face is PROPER if its three indices are pairwise distinct.  verts [V,3] DEVICE float32; a vertex with
+ *                  a coordinate that is not finite belongs to no cell: its label is -1 and no face naming it is a candidate.
+ *     Q2 grid      HOST arguments: the origin lo[3] (float32, finite), the cell edge h (float32, finite, > 0), the dims
+ *                  nx, ny, nz >= 1 with nx ny nz < 2^31.  The cell of a finite vertex per axis is
+ *                  c_i = floor(((double)x_i - (double)lo_i) / (double)h) clamped to [0, n_i - 1] (a vertex outside the grid
+ *                  belongs to the nearest border cell); its linear index is (c2 ny + c1) nx + c0.
+ *     Q3 clusters  a face is a CANDIDATE iff it is valid and proper, its three vertices are finite and they lie in three
+ *                  pairwise distinct cells.  A cell is USED iff some candidate names a vertex in it (the flag is set with a plain
+ *                  store of 1 by every such candidate: the racing stores write the same value).  A cluster's id is the rank of
+ *                  its cell among the used cells in ascending linear index, 0 .. K-1.  vert_cluster [V] int32 = the cluster id
+ *                  of the vertex's cell, -1 for a vertex in an unused cell or one that is not finite.  So the output has no
+ *                  vertex that no output face names, and a floater that collapses into one cell disappears whole.
+ *     Q4 members   the members of cluster k are ALL finite vertices in its cell (named by a candidate or not), in ascending
+ *                  vertex index; every sum below runs over them in that order, left to right, in one lane's loop.  The lists are
+ *                  built count -> scan -> fill through an integer atomic cursor -> a sort of every cluster's segment in place by
+ *                  its lane: insertion sort up to 32 entries, heap sort (O(k log k), no second buffer) beyond -- a coarse cell
+ *                  holds hundreds of vertices.
+ *     Q5 mean      per column of rows x [V,w] float32, 1 <= w <= 64:  s = 0;  s = s + x[v] over the members;  m = s / count;
+ *                  the output is (float)m.  Positions under placement `mean`, colours and any other attribute go through this
+ *                  one rule (nm_mesh_simplify_rows; the fill computes the positions itself).
+ *     Q6 quadric   needs inc_off / inc of nm_mesh_adjacency for the INPUT mesh, trusted as far as section 'mesh smooth' trusts
+ *                  them: an offset, a face index or a vertex index out of range is never followed, such an entry is skipped.
+ *                  m = the float64 mean of Q5 of the positions, unrounded.  A (symmetric, six entries) and b start at zero.  For
+ *                  each member v ascending and each face of v's list in list order, with its STORED corners (a, b, c):
+ *                  u = x[b] - x[a], w = x[c] - x[a];  n = cross(u, w) as S5 writes it;  e = x[a] - m;
+ *                  t = (n0 e0 + n1 e1) + n2 e2;  A_ij += n_i n_j for i <= j;  b_i += n_i t.  A face with j corners in the
+ *                  cluster is met j times and counts j times.  Then reg = ((A00 + A11) + A22) 2^-10 is added to A00, A11, A22;
+ *                  c00 = A11 A22 - A12 A12, c01 = A02 A12 - A01 A22, c02 = A01 A12 - A02 A11, c11 = A00 A22 - A02 A02,
+ *                  c12 = A01 A02 - A00 A12, c22 = A00 A11 - A01 A01;  det = (A00 c00 + A01 c01) + A02 c02;
+ *                  y_i = ((c_i0 b0 + c_i1 b1) + c_i2 b2) / det (c symmetric);  p = m + y.  The output is (float)p iff det is
+ *                  finite and > 0, p is finite and lo_i + c_i h <= p_i <= lo_i + (c_i + 1) h on every axis (float64, c_i the
+ *                  cluster's cell, each product rounded on its own); otherwise it is (float)m.  The regulariser makes a flat
+ *                  or straight neighbourhood solvable and slides its vertex towards the mean along the flat directions; the
+ *                  in-cell test keeps a runaway solution from leaving its cell.
+ *     Q7 faces     a candidate's corners are mapped through vert_cluster and rotated cyclically so that the smallest id comes
+ *                  first, which keeps the orientation.  A candidate f is dropped iff a candidate g < f has the same rotated
+ *                  triple; two faces over the same three clusters with OPPOSITE orientation have different triples and both
+ *                  stay (a sheet thinner than a cell keeps its two sides).  Kept faces come out in ascending input face index:
+ *                  faces_out [F',3] int32, face_src [F'] int32 (nullable) = new -> old face index.  The duplicates are found
+ *                  in an open-addressing table of 2 F slots of face indices: a free slot is claimed by compare-and-swap, a slot
+ *                  of the same triple lowered by an integer atomicMin, so a triple's slot ends with its lowest face.
+ *     Q8 calls     nm_mesh_simplify_count writes vert_cluster and reports {K, F', n_invalid, first_invalid} in ONE 32-byte
+ *                  read-back (a stream synchronise) and nothing else.  nm_mesh_simplify_fill writes verts_out [K,3], faces_out
+ *                  and face_src, placement 0 = mean or 1 = quadric; nm_mesh_simplify_rows averages rows [V,w] to out [K,w] by
+ *                  Q5.  Neither reads anything back nor synchronises: the count leaves its totals in the workspace AND
+ *                  remembers them on the host under the workspace's address (the 64 most recent workspaces, as C6), and both
+ *                  refuse a V, F, cell count, n_clusters or n_faces_out other than those.  K = 0 launches nothing (then F' = 0
+ *                  too), and an output of capacity 0 may be null.
+ *     Q9 determinism  every output is a function of the inputs alone, byte-identical from run to run.  Under a permutation of
+ *                  the rows of faces vert_cluster, K, the mean-placed vertices, the averaged rows and the SET of kept rotated
+ *                  triples do not change; quadric placement may move in its last bits, because its sums follow the lists'
+ *                  order, which is face order.  Only integer atomics whose result is order-independent are used (add,
+ *                  compare-and-swap of a free slot, min); the one order-dependent intermediate, a member list's order after the
+ *                  fill, is removed by the sort.  Nothing adds floats atomically.
+ *   workspace: DEVICE, 16-byte aligned, nm_mesh_simplify_workspace_bytes(V, F, nx, ny, nz) bytes = 16 bytes per vertex (cell,
+ *     cursor, offset, member) + 12 bytes per face (its rank, two table slots) + 4 bytes per cell (flag, then rank) + 16 bytes
+ *     per 1024 vertices, per 1024 faces and per 1024 cells (the scans' spans) + 68 and padding below 128: linear in V, F and
+ *     the cell count.  nm_mesh_simplify_count fills it; the other two entries take it with the same V, F and dims.
+ *   NM_ERR_ARG (with the entry's name in nm_last_error()) before any device work for a null required pointer (an array of no
+ *   rows may be null), V or 3 F negative or >= 2^31, a bad grid (lo or h not finite, h <= 0, a dim < 1, 2^31 cells or more),
+ *   width outside 1..64, an unknown placement, quadric placement without inc_off / inc, a workspace that is misaligned or
+ *   short, buffers that overlap (an output with another output, an input or the workspace), counts other than the count
+ *   phase left.
+ * ------------------------------------------------------------------------------------------- */
+int64_t nm_mesh_simplify_workspace_bytes(int64_t V, int64_t F, int nx, int ny, int nz);
+int nm_mesh_simplify_count(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo /* HOST [3] */, float h, int nx,
+                           int ny, int nz, int32_t* vert_cluster, void* workspace, int64_t workspace_bytes, int64_t* n_clusters,
+                           int64_t* n_faces_out, nm_stream_t stream);
+int nm_mesh_simplify_fill(const float* verts, int64_t V, const int32_t* faces, int64_t F, const float* lo /* HOST [3] */, float h, int nx,
+                          int ny, int nz, int placement, const int32_t* inc_off /* nullable unless quadric */,
+                          const int32_t* inc /* nullable unless quadric */, const void* workspace, int64_t workspace_bytes, float* verts_out,
+                          int32_t* faces_out, int32_t* face_src /* nullable */, int64_t n_clusters, int64_t n_faces_out,
+                          nm_stream_t stream);
+int nm_mesh_simplify_rows(const float* rows, int width, int64_t V, int64_t F, int nx, int ny, int nz, const void* workspace,
+                          int64_t workspace_bytes, float* out, int64_t n_clusters, nm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * SURVEY 8f-1 (first slice): device primitives of a training step of the background NeRF --
  *   reference trainers/vanilla_nerf_trainer.py:45-96 (forward with grad) + torch autograd's backward
  *   of models/vanilla.py:120-152 and utils/render_utils.py:69-105.  The layer loop is host code

@@ -241,6 +241,12 @@ SIGNATURES = {
     "nm_mesh_smooth": (i32, [c_f32p, i32, i64, c_i32p, i64, c_i32p, c_i32p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float, i32, c_f32p, c_f32p,
                              c_stream]),
     "nm_mesh_vertex_normals": (i32, [c_f32p, i64, i64, c_i32p, i64, c_i32p, c_i32p, c_f32p, c_stream]),
+    "nm_mesh_simplify_workspace_bytes": (i64, [i64, i64, i32, i32, i32]),
+    "nm_mesh_simplify_count": (i32, [c_f32p, i64, c_i32p, i64, ctypes.POINTER(ctypes.c_float), ctypes.c_float, i32, i32, i32, c_i32p, ctypes.c_void_p, i64,
+                                     ctypes.POINTER(i64), ctypes.POINTER(i64), c_stream]),
+    "nm_mesh_simplify_fill": (i32, [c_f32p, i64, c_i32p, i64, ctypes.POINTER(ctypes.c_float), ctypes.c_float, i32, i32, i32, i32, c_i32p, c_i32p,
+                                    ctypes.c_void_p, i64, c_f32p, c_i32p, c_i32p, i64, i64, c_stream]),
+    "nm_mesh_simplify_rows": (i32, [c_f32p, i32, i64, i64, i32, i32, i32, ctypes.c_void_p, i64, c_f32p, i64, c_stream]),
 }
 
 _lib = None

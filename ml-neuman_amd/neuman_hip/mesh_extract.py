@@ -21,7 +21,9 @@ components of a mesh, `select_components` compacts it to some of them and `clean
     verts, faces, normals, colours = extract_net_mesh(human.coarse_human_net, box, 128, level=10.0, largest=1, smooth=10)  # ... and smoothed
 
 `smooth=` runs neuman_hip.mesh_smooth (smooth_mesh, vertex_normals; csrc/mesh_smooth.hip, the header's 'mesh smooth', rules S1-S6) after the
-clean-up: Taubin iterations that take the grid-scale ripple off the surface and leave `faces` as they are.
+clean-up: Taubin iterations that take the grid-scale ripple off the surface and leave `faces` as they are.  `simplify=` then runs
+neuman_hip.mesh_simplify (simplify_mesh; csrc/mesh_simplify.hip, the header's 'mesh simplify', rules Q1-Q9): the vertices of every grid cell
+of that edge become one, placed by the quadrics of the faces around them, so that binding, posing and drawing pay for the detail one wants.
 
 The step after `clean_mesh` is neuman_hip.mesh_pose: `bind_mesh` binds the canonical mesh to the body, `pose_mesh` / `pose_mesh_frames` pose it
 for the frames of a sequence (csrc/mesh_pose.hip; the header's 'mesh pose', rules P1-P6)."""
@@ -260,17 +262,21 @@ def clean_mesh(verts, faces, *attrs, largest=1, min_faces=0):
     return select_components(verts, faces, comps, keep_mask(comps.n_faces, largest, min_faces), *attrs)
 
 
-def extract_net_mesh(net, aabb, res, level, colour=True, precision=None, slab_bytes=SLAB_BYTES, largest=None, min_faces=0, smooth=0):
+def extract_net_mesh(net, aabb, res, level, colour=True, precision=None, slab_bytes=SLAB_BYTES, largest=None, min_faces=0, smooth=0, simplify=0.0):
     """density_grid + extract_mesh on a static net (a background Joiner, or HumanNeRF.coarse_human_net with the box of
     occupancy.canonical_aabb) -> (verts, faces, normals, colours).  colour: per-vertex RGB [Nv,3] in [0, 1], the sigmoid of the net's own
     forward at the vertices seen along -normal (from outside, head on); the plain head takes no view.  Otherwise colours is None.
     largest / min_faces: clean_mesh's, run on (verts, faces, normals) before the colours, which are then evaluated at kept vertices only;
     the defaults keep everything.  smooth = n > 0: after the clean-up, n Taubin iterations of mesh_smooth.smooth_mesh on the vertices (faces
     unchanged) and the normals replaced by mesh_smooth.vertex_normals of the smoothed mesh; the colours are then evaluated at the smoothed
-    vertices along the new normals.  smooth = 0 changes nothing."""
+    vertices along the new normals.  smooth = 0 changes nothing.  simplify = h > 0: after the smoothing, mesh_simplify.simplify_mesh with
+    cells of edge h on the grid of `aabb` (quadric placement) and the normals replaced by mesh_smooth.vertex_normals of the simplified mesh;
+    the colours are then evaluated at the new vertices along them.  simplify = 0 changes nothing."""
     _check_clean(largest, min_faces)
     if isinstance(smooth, bool) or not isinstance(smooth, (int, np.integer)) or smooth < 0:
         raise ValueError(f"smooth must be an int >= 0 (Taubin iterations), got {smooth!r}")
+    if isinstance(simplify, bool) or not isinstance(simplify, (int, float, np.integer, np.floating)) or not np.isfinite(simplify) or simplify < 0:
+        raise ValueError(f"simplify must be a finite cell edge >= 0 (0: no simplification), got {simplify!r}")
     field = density_grid(net, aabb, res, precision=precision, slab_bytes=slab_bytes)
     verts, faces, normals = extract_mesh(field, aabb, level)
     if largest is not None or min_faces != 0:
@@ -280,6 +286,10 @@ def extract_net_mesh(net, aabb, res, level, colour=True, precision=None, slab_by
         adj = mesh_smooth.adjacency(faces, verts.shape[0])
         verts = mesh_smooth.smooth_mesh(verts, faces, int(smooth), adj=adj)
         normals = mesh_smooth.vertex_normals(verts, faces, adj=adj)
+    if simplify > 0:
+        from . import mesh_simplify, mesh_smooth                   # (they import this module)
+        verts, faces = mesh_simplify.simplify_mesh(verts, faces, float(simplify), aabb=aabb)
+        normals = mesh_smooth.vertex_normals(verts, faces)
     colours = None
     if colour:
         with torch.no_grad():

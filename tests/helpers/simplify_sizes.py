@@ -1,0 +1,122 @@
+"""The sizes at which the mesh simplification kernels (ml-neuman_amd/csrc/mesh_simplify.hip) change behaviour, and the meshes and grids
+tests/test_hip_mesh_simplify.py crosses them with.
+
+TABLE has the form of tests/helpers/mesh_sizes.py's: name -> (value, source file, pattern whose integer groups multiply to the value);
+tests/test_mesh_simplify_host.py checks on the CPU that every entry still reads so in the source and that every derived size lies past its
+threshold.  Everything here is numpy."""
+import types
+
+import numpy as np
+
+import smooth_sizes as SS
+
+CSRC = 'ml-neuman_amd/csrc/'
+TABLE = {
+    # sx_span_kernel: a workgroup scans kSpan counters (cells, clusters or faces), kSpan / kThreads consecutive ones per thread
+    'SPAN': (1024, CSRC + 'mesh_simplify.hip', r'constexpr int kSpan = (\d+);'),
+    # sx_scan_kernel: ONE workgroup of kThreads scans the spans' sums, ceil(spans / kThreads) spans per thread
+    'THREADS': (256, CSRC + 'mesh_simplify.hip', r'constexpr int kThreads = (\d+);'),
+    # sort_segment: a cluster of up to kSortInThread members by insertion, more by heap sort
+    'SORT': (32, CSRC + 'mesh_simplify.hip', r'constexpr int kSortInThread = (\d+);'),
+    # the duplicate table: kSlotsPerFace slots per input face; no bucket, so no threshold: what grows is the walk past taken slots
+    'SLOTS': (2, CSRC + 'mesh_simplify.hip', r'constexpr int kSlotsPerFace = (\d+);'),
+}
+C = types.SimpleNamespace(**{k: v[0] for k, v in TABLE.items()})
+SEED = 47
+
+UNIT_BOX = (-1.0, -1.0, -1.0, 1.0, 1.0, 1.0)                  # sharp_shapes' shapes are of unit scale
+STAR_CELLS = (0.17, 0.11, 0.3)                                # the issue's three cell sizes; at 0.3 the largest cluster has 97 members
+STAR_LARGEST_CLUSTER = 97
+
+OCTA_VERTS = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1]], np.float32)
+OCTA_FACES = np.array([[0, 2, 4], [2, 1, 4], [1, 3, 4], [3, 0, 4], [2, 0, 5], [1, 2, 5], [3, 1, 5], [0, 3, 5]], np.int32)      # outward
+OCTA_FINE = ((-1.5, -1.5, -1.5), 1.0, (3, 3, 3))              # (lo, h, dims): one cell per vertex
+OCTA_COARSE = ((-1.5, -1.5, -1.5), 3.0, (1, 1, 1))            # one cell for everything
+
+# ---- the scans --------------------------------------------------------------------------------------------------------------------------
+GRID_SMALL = SS.GRID_SMALL                                    # 3 x 683 = 2049 vertices, 2728 faces: three spans, the last holds one counter
+GRID_SMALL_CELL = 2.5                                         # 274 x 1 x 1 cells of 2.5 grid steps
+GRID_PAST_THE_SCAN = SS.GRID_PAST_THE_SCAN                    # 512 x 513 = 262 656 vertices: a scan thread owns two spans of vertices (and of faces)
+GRID_PAST_CELL = 3.0
+CELLS_PAST_THE_SCAN = (131, 67, 63)                           # tests/helpers/mesh_sizes.py's grid: 552 951 cells = 540 spans, three per scan thread
+CELLS_PAST_LO = (-0.655, -0.335, -0.315)                      # the torus (|x|, |y| <= 0.63, |z| <= 0.18) in cells of 0.01: y reaches past the grid
+CELLS_PAST_H = 0.01
+
+CROWD_JUST_PAST = C.SORT                                      # extra vertices in vertex 0's cell: with vertex 0 itself one member more than the insertion sort takes
+CROWD_FAR_PAST = 8 * C.SORT                                   # 257 members
+REPEATS = 300                                                 # every face of the octahedron this often: 300 faces contend for each of 8 slots
+
+
+def spans(n):
+    return (n + C.SPAN - 1) // C.SPAN
+
+
+def per_thread(n_spans):
+    return (n_spans + C.THREADS - 1) // C.THREADS
+
+
+def grid_of_mesh(verts, cell, margin=0.37):
+    """a grid of cell edge `cell` around verts whose origin is `margin` cells below the lowest vertex, so that no vertex lies on a cell's
+    face by construction -> (lo float32 [3], h float32, dims)"""
+    v = np.asarray(verts, np.float64)
+    v = v[np.isfinite(v).all(1)]
+    lo = (v.min(0) - margin * cell).astype(np.float32)
+    h = np.float32(cell)
+    dims = tuple(int(n) for n in np.floor((v.max(0) - lo.astype(np.float64)) / float(h)).astype(np.int64) + 1)
+    return lo, h, dims
+
+
+def crowded_octahedron(extra, seed=SEED):
+    """the octahedron, then `extra` vertices that no face names, all in vertex 0's cell of OCTA_FINE (x in [0.5, 1.5), |y|, |z| < 0.5): they
+    are members of its cluster and move its mean -> (verts, faces).  The vertex order is seeded, so the member list is filled out of order."""
+    rng = np.random.default_rng(seed + extra)
+    pts = np.stack([rng.uniform(0.55, 1.45, extra), rng.uniform(-0.45, 0.45, extra), rng.uniform(-0.45, 0.45, extra)], 1)
+    verts = np.concatenate([OCTA_VERTS, pts.astype(np.float32)])
+    perm = rng.permutation(verts.shape[0])                    # new index -> old
+    inv = np.argsort(perm)
+    return np.ascontiguousarray(verts[perm]), np.ascontiguousarray(inv[OCTA_FACES].astype(np.int32))
+
+
+def repeated_octahedron(repeats=REPEATS, seed=SEED):
+    """every face of the octahedron `repeats` times from seeded first corners, every fourth copy turned over, in seeded order -> faces
+    [8 repeats, 3]: 16 rotated triples in all"""
+    rng = np.random.default_rng(seed + 1)
+    f = np.repeat(OCTA_FACES.astype(np.int64), repeats, 0)
+    f = f[np.arange(f.shape[0])[:, None], (np.arange(3)[None] + rng.integers(0, 3, (f.shape[0], 1))) % 3]
+    turn = np.arange(f.shape[0]) % 4 == 3
+    f[turn] = f[turn][:, [0, 2, 1]]
+    return np.ascontiguousarray(f[rng.permutation(f.shape[0])].astype(np.int32))
+
+
+# ---- the hand-written mesh of the robustness cases: smooth_sizes' 21 vertices at chosen places ---------------------------------------------
+# tetrahedron A (0-3) and B (4-7, vertex 6 NaN) of edge ~2 cells, the strip 8-17 one cell per vertex, 18 unreferenced, 19 and 20 in a
+# degenerate face only; face 3 repeated as face 16
+def hand_mesh():
+    """-> (verts [21,3] float32, faces [18,3] int32, lo, h, dims): cells of edge 1"""
+    v = np.zeros((SS.HAND_VERTS, 3), np.float64)
+    tet = np.array([[0.2, 0.2, 0.2], [2.3, 0.3, 0.4], [0.4, 2.2, 0.3], [0.3, 0.4, 2.4]])
+    v[0:4] = tet
+    v[4:8] = tet + [4.0, 0.0, 0.0]
+    v[8:13] = np.stack([np.arange(5) + 0.5, np.full(5, 4.5), np.full(5, 0.5)], 1)
+    v[13:18] = np.stack([np.arange(5) + 0.6, np.full(5, 5.5), np.full(5, 0.6)], 1)
+    v[18] = (0.25, 0.3, 0.35)                                  # in vertex 0's cell: a member that no face names
+    v[19], v[20] = (6.5, 6.5, 3.5), (6.6, 6.4, 3.4)
+    verts = v.astype(np.float32)
+    verts[6, 1] = np.nan
+    return verts, SS.HAND_FACES.copy(), np.zeros(3, np.float32), np.float32(1.0), (7, 7, 4)
+
+
+# ---- the sphere of the extraction test ------------------------------------------------------------------------------------------------------
+SPHERE_BOX = SS.SPHERE_BOX
+SPHERE_DIMS = SS.SPHERE_DIMS                                  # 33^3 grid vertices: a grid step of 1 / 16
+SPHERE_CELL = 2.5 / 16                                        # 2.5 grid steps
+SPHERE_LO = (-1.013, -0.987, -1.021)                          # not aligned to the extraction's grid
+
+
+def sphere_mesh():
+    """isosurface_ref's extraction of a sphere on the 33^3 grid -> (verts, faces, lo, h, dims)"""
+    import isosurface_ref as IR
+    m = IR.extract(IR.sphere_field(SPHERE_DIMS, SPHERE_BOX, SS.SPHERE_CENTRE, SS.SPHERE_RADIUS), SPHERE_BOX, 0.0)
+    lo, h = np.asarray(SPHERE_LO, np.float32), np.float32(SPHERE_CELL)
+    dims = tuple(int(np.ceil((1.0 - float(l)) / float(h))) for l in lo)
+    return m['verts'], m['faces'].astype(np.int32), lo, h, dims
