@@ -9,30 +9,25 @@
 //                thread's link won.  A parent only ever decreases, so the root of a class ends as its smallest vertex under every interleaving
 //                (C3, C7).  flatten: every vertex points at its root.  Every launch after the first reads the invalid count and does nothing
 //                when it is not zero.
-//   rank         the three rankings (roots -> component ids, kept vertices -> new indices, kept faces -> output rows) share isosurface.hip's
-//                shape: a workgroup ranks a span of kSpan items (ballots inside a wave, LDS across the waves), ONE workgroup scans the spans'
-//                sums in 64 bits, a last launch adds the span's offset.  No look-back, no grid barrier, nothing waits for another workgroup.
+//   rank         the three rankings (roots -> component ids, kept vertices -> new indices, kept faces -> output rows) are mesh_device.h's:
+//                span_rank_kernel over a flag per item, span_scan_kernel over the spans' sums, a last launch here adds the span's offset.
 //   statistics   integer atomicAdd per vertex and per face; the boxes by atomicMin / atomicMax on the order-preserving integer image of a
 //                float, decoded in place by a last launch.  No float is ever added atomically.  The lanes of a wave that share a label are
 //                combined before the atomic (one body holds nearly every vertex: 10.5 ms without, profiles/mesh_components.md).
 //
 // Workspace: 9 bytes per vertex (parent, rank, referenced flag) + 4 bytes per face (rank) + 16 bytes per kSpan vertices and per kSpan faces + 64.
 #include "common.h"
-
-#include <mutex>
+#include "mesh_device.h"
 
 namespace {
 
-constexpr int kThreads = 256;                                 // every launch, the one-workgroup scan included
-constexpr int kSpan = 1024;                                   // items (vertices or faces) one workgroup of a ranking covers
-constexpr int kRounds = kSpan / kThreads;
-constexpr int64_t kHeaderBytes = 64;
+using namespace nm_mesh;                                      // the sizes, the header's protocol, the ranking, the checks: mesh_device.h
+
 constexpr int kCombine = 8;                                   // statistics: lanes of one label in a wave, from which their boxes are reduced by shuffles
-static_assert(kSpan % kThreads == 0 && kThreads % 64 == 0, "a span is whole rounds of whole waves");
 
 #define NM_RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-enum { kHdrComponents = 0, kHdrInvalid = 1, kHdrFirstInvalid = 2, kHdrVertsOut = 3, kHdrFacesOut = 4 };      // int64 words of the header
+enum { kHdrComponents = 0, kHdrVertsOut = 3, kHdrFacesOut = 4 };      // int64 words of the header beside kHdrInvalid and kHdrFirstInvalid
 
 // ---- workspace --------------------------------------------------------------------------------------------------------------------------
 struct Layout {
@@ -40,12 +35,10 @@ struct Layout {
     int64_t off_vsum, off_voff, off_fsum, off_foff, off_parent, off_rank, off_frank, off_ref, bytes;
 };
 
-inline int64_t up16(int64_t b) { return (b + 15) / 16 * 16; }
-
 inline Layout layout_of(int64_t V, int64_t F) {
     Layout L;
-    L.vspans = (V + kSpan - 1) / kSpan;
-    L.fspans = (F + kSpan - 1) / kSpan;
+    L.vspans = spans_of(V);
+    L.fspans = spans_of(F);
     L.off_vsum = kHeaderBytes;
     L.off_voff = L.off_vsum + L.vspans * 8;
     L.off_fsum = L.off_voff + L.vspans * 8;
@@ -82,15 +75,7 @@ inline Work work_of(void* ws, const Layout& L) {
     return w;
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
 // ---- label ------------------------------------------------------------------------------------------------------------------------------
-__global__ void mc_reset_kernel(int64_t* __restrict__ hdr) {
-    if (threadIdx.x < 8) hdr[threadIdx.x] = threadIdx.x == kHdrFirstInvalid ? INT64_MAX : 0;
-}
-
-__device__ __forceinline__ bool in_range(int32_t i, int64_t V) { return i >= 0 && (int64_t)i < V; }
-
 // rule C1: the range check comes before any use of an index.  `ref` was zeroed by the call.
 __global__ void __launch_bounds__(kThreads) mc_init_kernel(const int32_t* __restrict__ faces, int64_t F, int64_t V, int32_t* __restrict__ parent,
                                                            uint8_t* __restrict__ ref, int64_t* __restrict__ hdr) {
@@ -101,8 +86,7 @@ __global__ void __launch_bounds__(kThreads) mc_init_kernel(const int32_t* __rest
     if (in_range(a, V) && in_range(b, V) && in_range(c, V)) {
         ref[a] = 1; ref[b] = 1; ref[c] = 1;                   // (racing stores of the same byte value)
     } else {
-        atomicAdd(reinterpret_cast<unsigned long long*>(hdr + kHdrInvalid), 1ull);
-        atomicMin(reinterpret_cast<long long*>(hdr + kHdrFirstInvalid), (long long)i);
+        record_invalid_face(hdr, i);
     }
 }
 
@@ -158,74 +142,11 @@ __global__ void __launch_bounds__(kThreads) mc_flatten_kernel(int64_t V, int32_t
 }
 
 // ---- rank -------------------------------------------------------------------------------------------------------------------------------
-// the exclusive rank of this thread's flag among the workgroup's flags in thread order, after `carry` earlier ones; carry moves on by the total
-__device__ __forceinline__ int block_rank(bool flag, int& carry, int* s_wave) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long ballot = __ballot(flag);
-    if (lane == 0) s_wave[wave] = __popcll(ballot);
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) {
-        const int n = s_wave[w];
-        before += w < wave ? n : 0;
-        total += n;
-    }
-    const int r = carry + before + __popcll(ballot & ((1ull << lane) - 1ull));
-    carry += total;
-    __syncthreads();
-    return r;
-}
-
-// Pred: n items, flag(i) -> bool; rank_out[i] = the in-span rank of a flagged item, -1 of any other; span_sum[span] = flagged items of the span
-template <class Pred>
-__global__ void __launch_bounds__(kThreads) mc_span_kernel(Pred pred, int64_t n, int32_t* __restrict__ rank_out, int64_t* __restrict__ span_sum,
-                                                           const int64_t* __restrict__ skip_if) {
-    __shared__ int s_wave[kThreads / 64];
-    if (skip_if && *skip_if != 0) return;
-    const int64_t base = (int64_t)blockIdx.x * kSpan;
-    int carry = 0;
-#pragma unroll
-    for (int r = 0; r < kRounds; ++r) {
-        const int64_t i = base + r * kThreads + threadIdx.x;
-        const bool flag = i < n && pred.flag(i);
-        const int at = block_rank(flag, carry, s_wave);
-        if (i < n) rank_out[i] = flag ? at : -1;
-    }
-    if (threadIdx.x == 0) span_sum[blockIdx.x] = carry;
-}
-
-// exclusive scan of the spans' sums by one workgroup (isosurface.hip's iso_scan_kernel, one column): the total -> *total
-__global__ void __launch_bounds__(kThreads) mc_scan_kernel(const int64_t* __restrict__ span_sum, int64_t spans, int64_t* __restrict__ span_off,
-                                                           int64_t* __restrict__ total, const int64_t* __restrict__ skip_if) {
-    __shared__ int64_t part[kThreads];
-    if (skip_if && *skip_if != 0) return;
-    const int64_t per = (spans + kThreads - 1) / kThreads, lo = threadIdx.x * per, hi = lo + per < spans ? lo + per : spans;
-    int64_t s = 0;
-    for (int64_t i = lo; i < hi; ++i) s += span_sum[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t run = 0;
-        for (int i = 0; i < kThreads; ++i) {
-            const int64_t t = part[i];
-            part[i] = run;
-            run += t;
-        }
-        *total = run;
-    }
-    __syncthreads();
-    int64_t run = part[threadIdx.x];
-    for (int64_t i = lo; i < hi; ++i) {
-        span_off[i] = run;
-        run += span_sum[i];
-    }
-}
-
+// the sources of mesh_device.h's span_rank_kernel: count(i) is 1 for a flagged item, and with mark_empty the rank of any other reads -1
 struct IsRoot {                                               // rule C3: a representative is a referenced vertex that is its own root
     const int32_t* parent;
     const uint8_t* ref;
-    __device__ bool flag(int64_t v) const { return ref[v] != 0 && parent[v] == (int32_t)v; }
+    __device__ int count(int64_t v) const { return ref[v] != 0 && parent[v] == (int32_t)v; }
 };
 
 // rule C3: the id of a component is the rank of its root among the roots; a face has the label of its first vertex
@@ -353,14 +274,14 @@ struct Kept {                                                 // rule C5; a labe
 
 struct KeptVertex {
     Kept k;
-    __device__ bool flag(int64_t v) const { return k.vertex(v); }
+    __device__ int count(int64_t v) const { return k.vertex(v); }
 };
 
 struct KeptFace {                                             // a face has the label of its first vertex; an index out of range is never followed
     Kept k;
     const int32_t* faces;
     int64_t V;
-    __device__ bool flag(int64_t f) const {
+    __device__ int count(int64_t f) const {
         const int32_t a = faces[3 * f];
         return in_range(a, V) && k.vertex(a);
     }
@@ -396,55 +317,17 @@ __global__ void __launch_bounds__(kThreads) mc_select_fill_kernel(const int32_t*
     }
 }
 
-// What nm_mesh_select_count left in a workspace, remembered on the host by the workspace's address, so that nm_mesh_select_fill can compare
-// its counts without a read-back (rule C6): the last kRemembered workspaces.
+// What nm_mesh_select_count left in a workspace, for nm_mesh_select_fill to compare its counts with, without a read-back (rule C6)
 struct Selection {
     const void* workspace;
     int64_t V, F, n_verts_out, n_faces_out;
 };
-constexpr int kRemembered = 64;
-std::mutex g_selection_mutex;
-Selection g_selections[kRemembered] = {};
-int g_selection_next = 0;
-
-void remember_selection(const Selection& s) {
-    std::lock_guard<std::mutex> lock(g_selection_mutex);
-    for (int i = 0; i < kRemembered; ++i)
-        if (g_selections[i].workspace == s.workspace) {
-            g_selections[i] = s;
-            return;
-        }
-    g_selections[g_selection_next] = s;
-    g_selection_next = (g_selection_next + 1) % kRemembered;
-}
-
-void forget_selection(const void* workspace) {
-    std::lock_guard<std::mutex> lock(g_selection_mutex);
-    for (int i = 0; i < kRemembered; ++i)
-        if (g_selections[i].workspace == workspace) g_selections[i] = Selection{};
-}
-
-bool recall_selection(const void* workspace, Selection* out) {
-    std::lock_guard<std::mutex> lock(g_selection_mutex);
-    for (int i = 0; i < kRemembered; ++i)
-        if (g_selections[i].workspace == workspace) {
-            *out = g_selections[i];
-            return true;
-        }
-    return false;
-}
+Remembered<Selection> g_selections;
 
 // ---- argument checks --------------------------------------------------------------------------------------------------------------------
-inline bool count_ok(int64_t n) { return n >= 0 && n < (1ll << 31); }
-
 #define NM_MC_SIZES(who)                                                                                                                     \
     NM_REQUIRE(count_ok(V) && count_ok(F), who ": V = %lld, F = %lld: both must be in [0, 2^31)", (long long)V, (long long)F);              \
     NM_REQUIRE(faces || F == 0, who ": null faces")
-#define NM_MC_WORKSPACE(who)                                                                                                                 \
-    NM_REQUIRE(workspace, who ": null workspace");                                                                                           \
-    NM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, who ": workspace must be 16-byte aligned");                              \
-    NM_REQUIRE(workspace_bytes >= layout_of(V, F).bytes, who ": workspace of %lld bytes, %lld needed", (long long)workspace_bytes,          \
-               (long long)layout_of(V, F).bytes)
 #define NM_MC_LABELS(who)                                                                                                                    \
     NM_REQUIRE(vert_label || V == 0, who ": null vert_label");                                                                               \
     NM_REQUIRE(count_ok(C), who ": C = %lld must be in [0, 2^31)", (long long)C)
@@ -466,8 +349,8 @@ int nm_mesh_components(const int32_t* faces, int64_t F, int64_t V, int32_t* vert
     NM_MC_SIZES("nm_mesh_components");
     NM_REQUIRE(vert_label || V == 0, "nm_mesh_components: null vert_label");
     NM_REQUIRE(n_components, "nm_mesh_components: null count pointer");
-    NM_MC_WORKSPACE("nm_mesh_components");
-    forget_selection(workspace);                               // the arrays of a selection are overwritten
+    NM_MESH_WORKSPACE("nm_mesh_components", layout_of(V, F).bytes);
+    g_selections.forget(workspace);                               // the arrays of a selection are overwritten
     if (V == 0 && F == 0) {
         *n_components = 0;
         return NM_OK;
@@ -477,25 +360,23 @@ int nm_mesh_components(const int32_t* faces, int64_t F, int64_t V, int32_t* vert
     hipStream_t st = nm::as_stream(stream);
     int rc = NM_OK;
     if (V > 0 && (rc = nm::check_hip(hipMemsetAsync(w.ref, 0, (size_t)V, st), "nm_mesh_components: clear flags"))) return rc;
-    hipLaunchKernelGGL(mc_reset_kernel, dim3(1), dim3(64), 0, st, w.hdr);
+    hipLaunchKernelGGL(reset_header_kernel, dim3(1), dim3(64), 0, st, w.hdr);
     hipLaunchKernelGGL(mc_init_kernel, dim3(blocks_for(V > F ? V : F)), dim3(kThreads), 0, st, faces, F, V, w.parent, w.ref, w.hdr);
     if (V > 0 && F > 0) {
         hipLaunchKernelGGL(mc_hook_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, faces, F, w.parent, w.hdr);
         hipLaunchKernelGGL(mc_flatten_kernel, dim3(blocks_for(V)), dim3(kThreads), 0, st, V, w.parent, w.hdr);
     }
     if (V > 0) {
-        hipLaunchKernelGGL(mc_span_kernel<IsRoot>, dim3((unsigned)L.vspans), dim3(kThreads), 0, st, IsRoot{w.parent, w.ref}, V, w.rank, w.vsum,
+        hipLaunchKernelGGL(span_rank_kernel<IsRoot>, dim3((unsigned)L.vspans), dim3(kThreads), 0, st, IsRoot{w.parent, w.ref}, V, w.rank, 1, w.vsum,
                            w.hdr + kHdrInvalid);
-        hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.vsum, L.vspans, w.voff, w.hdr + kHdrComponents, w.hdr + kHdrInvalid);
+        hipLaunchKernelGGL(span_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.vsum, L.vspans, w.voff, w.hdr + kHdrComponents, nullptr,
+                           w.hdr + kHdrInvalid);
         hipLaunchKernelGGL(mc_label_kernel, dim3(blocks_for(V > F ? V : F)), dim3(kThreads), 0, st, faces, F, V, w.parent, w.ref, w.rank, w.voff, w.hdr,
                            vert_label, face_label);
     }
     if ((rc = nm::check_launch("mesh component kernels"))) return rc;
     int64_t head[3] = {0, 0, 0};                               // the one read-back: {n_components, n_invalid, first_invalid}
-    if ((rc = nm::check_hip(hipMemcpyAsync(head, w.hdr, sizeof(head), hipMemcpyDeviceToHost, st), "nm_mesh_components: read counts"))) return rc;
-    if ((rc = nm::check_hip(hipStreamSynchronize(st), "nm_mesh_components: sync"))) return rc;
-    NM_REQUIRE(head[kHdrInvalid] == 0, "nm_mesh_components: %lld invalid faces (an index outside [0, %lld)), the first of them face %lld",
-               (long long)head[kHdrInvalid], (long long)V, (long long)head[kHdrFirstInvalid]);
+    if ((rc = read_header("nm_mesh_components", w.hdr, head, 3, V, st))) return rc;
     *n_components = head[kHdrComponents];
     return NM_OK;
 }
@@ -522,8 +403,8 @@ int nm_mesh_select_count(const int32_t* faces, int64_t F, int64_t V, const int32
     NM_MC_LABELS("nm_mesh_select_count");
     NM_REQUIRE(keep || C == 0, "nm_mesh_select_count: null keep");
     NM_REQUIRE(n_verts_out && n_faces_out, "nm_mesh_select_count: null count pointer");
-    NM_MC_WORKSPACE("nm_mesh_select_count");
-    forget_selection(workspace);
+    NM_MESH_WORKSPACE("nm_mesh_select_count", layout_of(V, F).bytes);
+    g_selections.forget(workspace);
     const Layout L = layout_of(V, F);
     const Work w = work_of(workspace, L);
     hipStream_t st = nm::as_stream(stream);
@@ -531,19 +412,19 @@ int nm_mesh_select_count(const int32_t* faces, int64_t F, int64_t V, const int32
     int64_t counts[2] = {0, 0};
     if (V > 0) {
         const Kept k = {vert_label, keep, C};
-        hipLaunchKernelGGL(mc_reset_kernel, dim3(1), dim3(64), 0, st, w.hdr);
-        hipLaunchKernelGGL(mc_span_kernel<KeptVertex>, dim3((unsigned)L.vspans), dim3(kThreads), 0, st, KeptVertex{k}, V, w.rank, w.vsum, nullptr);
-        hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.vsum, L.vspans, w.voff, w.hdr + kHdrVertsOut, nullptr);
+        hipLaunchKernelGGL(reset_header_kernel, dim3(1), dim3(64), 0, st, w.hdr);
+        hipLaunchKernelGGL(span_rank_kernel<KeptVertex>, dim3((unsigned)L.vspans), dim3(kThreads), 0, st, KeptVertex{k}, V, w.rank, 1, w.vsum, nullptr);
+        hipLaunchKernelGGL(span_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.vsum, L.vspans, w.voff, w.hdr + kHdrVertsOut, nullptr, nullptr);
         if (F > 0) {
-            hipLaunchKernelGGL(mc_span_kernel<KeptFace>, dim3((unsigned)L.fspans), dim3(kThreads), 0, st, KeptFace{k, faces, V}, F, w.frank, w.fsum, nullptr);
-            hipLaunchKernelGGL(mc_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.fsum, L.fspans, w.foff, w.hdr + kHdrFacesOut, nullptr);
+            hipLaunchKernelGGL(span_rank_kernel<KeptFace>, dim3((unsigned)L.fspans), dim3(kThreads), 0, st, KeptFace{k, faces, V}, F, w.frank, 1, w.fsum, nullptr);
+            hipLaunchKernelGGL(span_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.fsum, L.fspans, w.foff, w.hdr + kHdrFacesOut, nullptr, nullptr);
         }
         hipLaunchKernelGGL(mc_select_offset_kernel, dim3(blocks_for(V > F ? V : F)), dim3(kThreads), 0, st, V, F, w.rank, w.frank, w.voff, w.foff);
         if ((rc = nm::check_launch("mesh selection count kernels"))) return rc;
         if ((rc = nm::check_hip(hipMemcpyAsync(counts, w.hdr + kHdrVertsOut, 16, hipMemcpyDeviceToHost, st), "nm_mesh_select_count: read counts"))) return rc;
         if ((rc = nm::check_hip(hipStreamSynchronize(st), "nm_mesh_select_count: sync"))) return rc;     // the one read-back
     }
-    remember_selection(Selection{workspace, V, F, counts[0], counts[1]});
+    g_selections.remember(Selection{workspace, V, F, counts[0], counts[1]});
     *n_verts_out = counts[0];
     *n_faces_out = counts[1];
     return NM_OK;
@@ -554,11 +435,11 @@ int nm_mesh_select_fill(const int32_t* faces, int64_t F, int64_t V, const int32_
     NM_MC_SIZES("nm_mesh_select_fill");
     NM_MC_LABELS("nm_mesh_select_fill");
     NM_REQUIRE(keep || C == 0, "nm_mesh_select_fill: null keep");
-    NM_MC_WORKSPACE("nm_mesh_select_fill");
+    NM_MESH_WORKSPACE("nm_mesh_select_fill", layout_of(V, F).bytes);
     NM_REQUIRE(count_ok(n_verts_out) && count_ok(n_faces_out), "nm_mesh_select_fill: bad counts %lld, %lld", (long long)n_verts_out, (long long)n_faces_out);
     NM_REQUIRE((vert_src || n_verts_out == 0) && (faces_out || n_faces_out == 0), "nm_mesh_select_fill: null output");      // (an empty tensor's pointer is null)
     Selection s;
-    NM_REQUIRE(recall_selection(workspace, &s) && s.V == V && s.F == F,
+    NM_REQUIRE(g_selections.recall(workspace, &s) && s.V == V && s.F == F,
                "nm_mesh_select_fill: the workspace holds no selection of this mesh (run nm_mesh_select_count on it first)");
     NM_REQUIRE(s.n_verts_out == n_verts_out && s.n_faces_out == n_faces_out,
                "nm_mesh_select_fill: counts %lld vertices, %lld faces; nm_mesh_select_count left %lld, %lld in the workspace", (long long)n_verts_out,

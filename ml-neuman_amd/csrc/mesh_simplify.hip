@@ -7,8 +7,8 @@
 //   count        cells: a thread per vertex, the cell of rule Q2 (-1: a coordinate that is not finite).  mark: every face range-checked BEFORE
 //                anything is indexed (invalid faces counted, their lowest index kept); a candidate stores 1 into its three cells' flags.
 //                The three rankings (used cells -> cluster ids, clusters' member counts -> the member lists' offsets, kept faces -> output
-//                rows) share one scan of mesh_smooth.hip's shape: a workgroup scans a span of kSpan counters, ONE workgroup scans the spans'
-//                sums in 64 bits, the consumer adds the span's offset.  members: count per cluster -> scan -> fill through an integer
+//                rows) share mesh_device.h's scan: span_rank_kernel over a span of kSpan counters, span_scan_kernel over the spans' sums in 64
+//                bits, the consumer adds the span's offset.  members: count per cluster -> scan -> fill through an integer
 //                atomicAdd on the cursor -> a sort of every cluster's segment in place by one lane (insertion up to kSortInThread entries,
 //                heap sort beyond), which makes the lists a function of the mesh alone.  duplicates: an open-addressing table of face
 //                indices, 2 slots per face; a slot's key is the rotated triple of the face it holds, claimed by compare-and-swap and lowered
@@ -20,21 +20,17 @@
 // Workspace: 16 bytes per vertex (cell, cursor, offset, member) + 12 bytes per face (rank, two table slots) + 4 bytes per cell (flag, then
 // rank) + 16 bytes per kSpan vertices, faces and cells + 68.
 #include "common.h"
+#include "mesh_device.h"
 
 #include <cmath>
-#include <mutex>
 
 namespace {
 
-constexpr int kThreads = 256;                                 // every launch, the one-workgroup scan included
-constexpr int kSpan = 1024;                                   // counters one workgroup of the scan covers
-constexpr int kPerThread = kSpan / kThreads;                  // consecutive counters of one thread
-constexpr int kSortInThread = 32;                             // a segment of up to this many entries: insertion sort; longer: heap sort
-constexpr int kSlotsPerFace = 2;                              // the duplicate table: slots per input face (at most half of them are ever taken)
-constexpr int64_t kHeaderBytes = 64;
-static_assert(kSpan % kThreads == 0 && kThreads % 64 == 0, "a span is whole threads' shares, a workgroup whole waves");
+using namespace nm_mesh;                                      // the sizes, the header's protocol, the scan, the sort, the checks, the records: mesh_device.h
 
-enum { kHdrClusters = 0, kHdrFacesOut = 1, kHdrInvalid = 2, kHdrFirstInvalid = 3, kHdrMembers = 4 };      // int64 words of the header
+constexpr int kSlotsPerFace = 2;                              // the duplicate table: slots per input face (at most half of them are ever taken)
+
+enum { kHdrClusters = 0, kHdrFacesOut = 3, kHdrMembers = 4 };      // int64 words of the header beside kHdrInvalid and kHdrFirstInvalid
 enum { kPlaceMean = 0, kPlaceQuadric = 1 };
 
 struct Grid {                                                 // rule Q2
@@ -47,9 +43,6 @@ struct Layout {
     int64_t cells, cspans, vspans, fspans, slots;
     int64_t off_csum, off_coff, off_vsum, off_voff, off_fsum, off_foff, off_vcell, off_cursor, off_moff, off_mem, off_crank, off_frank, off_table, bytes;
 };
-
-inline int64_t up16(int64_t b) { return (b + 15) / 16 * 16; }
-inline int64_t spans_of(int64_t n) { return (n + kSpan - 1) / kSpan; }
 
 inline Layout layout_of(int64_t V, int64_t F, int64_t cells) {
     Layout L;
@@ -113,17 +106,10 @@ inline Work work_of(const void* ws, const Layout& L, int64_t V, int64_t F, const
     return w;
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-__device__ __forceinline__ bool in_range(int32_t i, int64_t n) { return i >= 0 && (int64_t)i < n; }
 __device__ __forceinline__ bool finite_f(float x) { return fabsf(x) <= 3.402823466e+38f; }             // (a NaN compares false)
 __device__ __forceinline__ bool finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }
 
 // ---- cells and candidates ---------------------------------------------------------------------------------------------------------------
-__global__ void sx_reset_kernel(int64_t* __restrict__ hdr) {
-    if (threadIdx.x < 8) hdr[threadIdx.x] = threadIdx.x == kHdrFirstInvalid ? INT64_MAX : 0;
-}
-
 // rule Q2: floor((x - lo) / h) in float64, clamped while still a double (a far vertex must not overflow the conversion)
 __global__ void __launch_bounds__(kThreads) sx_cell_kernel(const float* __restrict__ verts, int64_t V, Grid g, int32_t* __restrict__ vcell) {
     const int64_t v = (int64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -159,8 +145,7 @@ __global__ void __launch_bounds__(kThreads) sx_mark_kernel(const int32_t* __rest
     if (f >= F) return;
     const int32_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
     if (!(in_range(a, V) && in_range(b, V) && in_range(c, V))) {
-        atomicAdd(reinterpret_cast<unsigned long long*>(hdr + kHdrInvalid), 1ull);
-        atomicMin(reinterpret_cast<long long*>(hdr + kHdrFirstInvalid), (long long)f);
+        record_invalid_face(hdr, f);
         return;
     }
     int32_t cell[3];
@@ -168,73 +153,6 @@ __global__ void __launch_bounds__(kThreads) sx_mark_kernel(const int32_t* __rest
 #pragma unroll
     for (int k = 0; k < 3; ++k)
         if ((int64_t)cell[k] < cells) used[cell[k]] = 1;
-}
-
-// ---- the scan ---------------------------------------------------------------------------------------------------------------------------
-// the exclusive scan of a span's counters inside the span, and the span's sum.  `out` may be `count` itself: a thread reads its own counters
-// before it writes them.  mark_empty: a zero counter's entry reads -1 (a flag's rank is asked for only where the flag is set).
-__global__ void __launch_bounds__(kThreads) sx_span_kernel(const int32_t* count, int64_t n, int32_t* out, int mark_empty, int64_t* __restrict__ span_sum,
-                                                           const int64_t* __restrict__ hdr) {
-    __shared__ int s_wave[kThreads / 64];
-    if (hdr[kHdrInvalid] != 0) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t first = (int64_t)blockIdx.x * kSpan + (int64_t)threadIdx.x * kPerThread;
-    int c[kPerThread], mine = 0;
-#pragma unroll
-    for (int r = 0; r < kPerThread; ++r) {
-        c[r] = first + r < n ? count[first + r] : 0;
-        mine += c[r];
-    }
-    int incl = mine;                                           // inclusive scan of the threads' shares across the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) {
-        const int m = s_wave[w];
-        before += w < wave ? m : 0;
-        total += m;
-    }
-    int run = before + incl - mine;
-#pragma unroll
-    for (int r = 0; r < kPerThread; ++r) {
-        if (first + r < n) out[first + r] = (mark_empty && c[r] == 0) ? -1 : run;
-        run += c[r];
-    }
-    if (threadIdx.x == 0) span_sum[blockIdx.x] = total;
-}
-
-// exclusive scan of the spans' sums by one workgroup (mesh_components.hip's mc_scan_kernel): the total -> *total and, if given, *end
-__global__ void __launch_bounds__(kThreads) sx_scan_kernel(const int64_t* __restrict__ span_sum, int64_t spans, int64_t* __restrict__ span_off,
-                                                           int64_t* total, int32_t* __restrict__ end, const int64_t* hdr) {
-    __shared__ int64_t part[kThreads];
-    if (hdr[kHdrInvalid] != 0) return;
-    const int64_t per = (spans + kThreads - 1) / kThreads, lo = threadIdx.x * per, hi = lo + per < spans ? lo + per : spans;
-    int64_t s = 0;
-    for (int64_t i = lo; i < hi; ++i) s += span_sum[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t run = 0;
-        for (int i = 0; i < kThreads; ++i) {
-            const int64_t t = part[i];
-            part[i] = run;
-            run += t;
-        }
-        *total = run;
-        if (end) *end = (int32_t)run;                          // (at most V < 2^31)
-    }
-    __syncthreads();
-    int64_t run = part[threadIdx.x];
-    for (int64_t i = lo; i < hi; ++i) {
-        span_off[i] = run;
-        run += span_sum[i];
-    }
 }
 
 // ---- clusters and members ---------------------------------------------------------------------------------------------------------------
@@ -274,51 +192,6 @@ __global__ void __launch_bounds__(kThreads) sx_member_kernel(Work w) {
     if (!in_range(k, w.V)) return;
     const int64_t at = atomicAdd(w.cursor + k, 1);
     if (at >= 0 && at < w.V) w.mem[at] = (int32_t)v;
-}
-
-// ascending, in place, by one lane: insertion sort up to kSortInThread entries, heap sort beyond (mesh_smooth.hip's sort_segment)
-__device__ void sort_segment(int32_t* a, int n) {
-    if (n <= kSortInThread) {
-        for (int i = 1; i < n; ++i) {
-            const int32_t x = a[i];
-            int j = i;
-            while (j > 0 && a[j - 1] > x) {
-                a[j] = a[j - 1];
-                --j;
-            }
-            a[j] = x;
-        }
-        return;
-    }
-    for (int start = n / 2 - 1, end = n; end > 1;) {          // heap construction (start counts down to 0), then n - 1 extractions
-        int root;
-        int32_t x;
-        if (start >= 0) {
-            root = start--;
-            x = a[root];
-        } else {
-            --end;
-            x = a[end];
-            a[end] = a[0];
-            root = 0;
-        }
-        while (true) {                                         // sift x down from the hole at root, inside [0, end)
-            int child = 2 * root + 1;
-            if (child >= end) break;
-            int32_t cv = a[child];
-            if (child + 1 < end) {
-                const int32_t other = a[child + 1];
-                if (other > cv) {
-                    cv = other;
-                    ++child;
-                }
-            }
-            if (cv <= x) break;
-            a[root] = cv;
-            root = child;
-        }
-        a[root] = x;
-    }
 }
 
 // rule Q4: a cluster's members in ascending vertex index (entries past K have empty segments)
@@ -522,47 +395,14 @@ __global__ void __launch_bounds__(kThreads) sx_rows_kernel(Work w, const float* 
     out[e] = (float)(s / (double)(hi - lo));
 }
 
-// What nm_mesh_simplify_count left in a workspace, remembered on the host by the workspace's address, so that the fill and the rows entry can
-// compare their counts without a read-back (rule Q8; mesh_components.hip's record of a selection): the last kRemembered workspaces.
+// What nm_mesh_simplify_count left in a workspace, for the fill and the rows entry to compare their counts with, without a read-back (rule Q8)
 struct Record {
     const void* workspace;
     int64_t V, F, cells, n_clusters, n_faces_out;
 };
-constexpr int kRemembered = 64;
-std::mutex g_record_mutex;
-Record g_records[kRemembered] = {};
-int g_record_next = 0;
-
-void remember(const Record& r) {
-    std::lock_guard<std::mutex> lock(g_record_mutex);
-    for (int i = 0; i < kRemembered; ++i)
-        if (g_records[i].workspace == r.workspace) {
-            g_records[i] = r;
-            return;
-        }
-    g_records[g_record_next] = r;
-    g_record_next = (g_record_next + 1) % kRemembered;
-}
-
-void forget(const void* workspace) {
-    std::lock_guard<std::mutex> lock(g_record_mutex);
-    for (int i = 0; i < kRemembered; ++i)
-        if (g_records[i].workspace == workspace) g_records[i] = Record{};
-}
-
-bool recall(const void* workspace, Record* out) {
-    std::lock_guard<std::mutex> lock(g_record_mutex);
-    for (int i = 0; i < kRemembered; ++i)
-        if (g_records[i].workspace == workspace) {
-            *out = g_records[i];
-            return true;
-        }
-    return false;
-}
+Remembered<Record> g_records;
 
 // ---- argument checks --------------------------------------------------------------------------------------------------------------------
-inline bool count_ok(int64_t n) { return n >= 0 && n < (1ll << 31); }
-inline bool mesh_ok(int64_t V, int64_t F) { return count_ok(V) && F >= 0 && F < (1ll << 31) && count_ok(3 * F); }
 inline bool dims_ok(int nx, int ny, int nz) { return nx >= 1 && ny >= 1 && nz >= 1 && (int64_t)nx * ny < (1ll << 31) && (int64_t)nx * ny * nz < (1ll << 31); }
 inline bool grid_ok(const float* lo, float h, int nx, int ny, int nz) {
     return lo && std::isfinite(lo[0]) && std::isfinite(lo[1]) && std::isfinite(lo[2]) && std::isfinite(h) && h > 0.f && dims_ok(nx, ny, nz);
@@ -578,29 +418,6 @@ inline Grid grid_of(const float* lo, float h, int nx, int ny, int nz) {
     return g;
 }
 
-// two byte ranges share a byte (a null pointer or an empty range shares nothing)
-inline bool overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-    if (!a || !b || a_bytes <= 0 || b_bytes <= 0) return false;
-    const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-    return p < q + (uintptr_t)b_bytes && q < p + (uintptr_t)a_bytes;
-}
-
-struct Range {
-    const void* p;
-    int64_t bytes;
-};
-
-// every range of `outs` against every other range of `outs` and every range of `ins`
-inline bool any_overlap(const Range* outs, int n_outs, const Range* ins, int n_ins) {
-    for (int i = 0; i < n_outs; ++i) {
-        for (int j = i + 1; j < n_outs; ++j)
-            if (overlap(outs[i].p, outs[i].bytes, outs[j].p, outs[j].bytes)) return true;
-        for (int j = 0; j < n_ins; ++j)
-            if (overlap(outs[i].p, outs[i].bytes, ins[j].p, ins[j].bytes)) return true;
-    }
-    return false;
-}
-
 #define NM_SX_MESH(who)                                                                                                                      \
     NM_REQUIRE(mesh_ok(V, F), who ": V = %lld, F = %lld: V and 3 F must be in [0, 2^31)", (long long)V, (long long)F);                      \
     NM_REQUIRE(faces || F == 0, who ": null faces");                                                                                         \
@@ -608,10 +425,6 @@ inline bool any_overlap(const Range* outs, int n_outs, const Range* ins, int n_i
 #define NM_SX_GRID(who)                                                                                                                      \
     NM_REQUIRE(grid_ok(lo, h, nx, ny, nz), who ": bad grid: lo must be three finite floats, h finite and > 0 (h = %g), dims >= 1 with fewer " \
                "than 2^31 cells (%d x %d x %d)", (double)h, nx, ny, nz)
-#define NM_SX_WORKSPACE(who)                                                                                                                 \
-    NM_REQUIRE(workspace, who ": null workspace");                                                                                           \
-    NM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, who ": workspace must be 16-byte aligned");                              \
-    NM_REQUIRE(workspace_bytes >= L.bytes, who ": workspace of %lld bytes, %lld needed", (long long)workspace_bytes, (long long)L.bytes)
 
 }  // namespace
 
@@ -634,27 +447,28 @@ int nm_mesh_simplify_count(const float* verts, int64_t V, const int32_t* faces, 
     NM_REQUIRE(vert_cluster || V == 0, "nm_mesh_simplify_count: null vert_cluster");
     NM_REQUIRE(n_clusters && n_faces_out, "nm_mesh_simplify_count: null count pointer");
     const Layout L = layout_of(V, F, (int64_t)nx * ny * nz);
-    NM_SX_WORKSPACE("nm_mesh_simplify_count");
+    NM_MESH_WORKSPACE("nm_mesh_simplify_count", L.bytes);
     {
         const Range outs[2] = {{vert_cluster, V * 4}, {workspace, L.bytes}}, ins[2] = {{verts, V * 12}, {faces, F * 12}};
         NM_REQUIRE(!any_overlap(outs, 2, ins, 2), "nm_mesh_simplify_count: verts, faces, vert_cluster and the workspace must not overlap");
     }
-    forget(workspace);
+    g_records.forget(workspace);
     const Work w = work_of(workspace, L, V, F, grid_of(lo, h, nx, ny, nz));
     hipStream_t st = nm::as_stream(stream);
     int rc = NM_OK;
     if ((rc = nm::check_hip(hipMemsetAsync(w.crank, 0, (size_t)L.cells * 4, st), "nm_mesh_simplify_count: clear cell flags"))) return rc;
     if (V > 0 && (rc = nm::check_hip(hipMemsetAsync(w.cursor, 0, (size_t)V * 4, st), "nm_mesh_simplify_count: clear counters"))) return rc;
     if (F > 0 && (rc = nm::check_hip(hipMemsetAsync(w.table, 0xFF, (size_t)L.slots * 4, st), "nm_mesh_simplify_count: clear table"))) return rc;
-    hipLaunchKernelGGL(sx_reset_kernel, dim3(1), dim3(64), 0, st, w.hdr);
+    hipLaunchKernelGGL(reset_header_kernel, dim3(1), dim3(64), 0, st, w.hdr);
     if (V > 0) hipLaunchKernelGGL(sx_cell_kernel, dim3(blocks_for(V)), dim3(kThreads), 0, st, verts, V, w.g, w.vcell);
     if (F > 0) hipLaunchKernelGGL(sx_mark_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, faces, F, V, w.vcell, L.cells, w.crank, w.hdr);
-    hipLaunchKernelGGL(sx_span_kernel, dim3((unsigned)L.cspans), dim3(kThreads), 0, st, w.crank, L.cells, w.crank, 1, w.csum, w.hdr);
-    hipLaunchKernelGGL(sx_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.csum, L.cspans, w.coff, w.hdr + kHdrClusters, (int32_t*)nullptr, w.hdr);
+    const int64_t* const invalid = w.hdr + kHdrInvalid;       // every scan launch is skipped when this word is not zero
+    hipLaunchKernelGGL(span_rank_kernel<Counters>, dim3((unsigned)L.cspans), dim3(kThreads), 0, st, Counters{w.crank}, L.cells, w.crank, 1, w.csum, invalid);
+    hipLaunchKernelGGL(span_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.csum, L.cspans, w.coff, w.hdr + kHdrClusters, nullptr, invalid);
     if (V > 0) {
         hipLaunchKernelGGL(sx_cluster_kernel, dim3(blocks_for(V)), dim3(kThreads), 0, st, w, vert_cluster);
-        hipLaunchKernelGGL(sx_span_kernel, dim3((unsigned)L.vspans), dim3(kThreads), 0, st, w.cursor, V, w.moff, 0, w.vsum, w.hdr);
-        hipLaunchKernelGGL(sx_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.vsum, L.vspans, w.voff, w.hdr + kHdrMembers, w.moff + V, w.hdr);
+        hipLaunchKernelGGL(span_rank_kernel<Counters>, dim3((unsigned)L.vspans), dim3(kThreads), 0, st, Counters{w.cursor}, V, w.moff, 0, w.vsum, invalid);
+        hipLaunchKernelGGL(span_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.vsum, L.vspans, w.voff, w.hdr + kHdrMembers, w.moff + V, invalid);
         hipLaunchKernelGGL(sx_offset_kernel, dim3(blocks_for(V)), dim3(kThreads), 0, st, w);
         hipLaunchKernelGGL(sx_member_kernel, dim3(blocks_for(V)), dim3(kThreads), 0, st, w);
         hipLaunchKernelGGL(sx_sort_kernel, dim3(blocks_for(V)), dim3(kThreads), 0, st, w);
@@ -662,16 +476,13 @@ int nm_mesh_simplify_count(const float* verts, int64_t V, const int32_t* faces, 
     if (F > 0 && V > 0) {
         hipLaunchKernelGGL(sx_insert_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, w, faces);
         hipLaunchKernelGGL(sx_keep_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, w, faces);
-        hipLaunchKernelGGL(sx_span_kernel, dim3((unsigned)L.fspans), dim3(kThreads), 0, st, w.frank, F, w.frank, 1, w.fsum, w.hdr);
-        hipLaunchKernelGGL(sx_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.fsum, L.fspans, w.foff, w.hdr + kHdrFacesOut, (int32_t*)nullptr, w.hdr);
+        hipLaunchKernelGGL(span_rank_kernel<Counters>, dim3((unsigned)L.fspans), dim3(kThreads), 0, st, Counters{w.frank}, F, w.frank, 1, w.fsum, invalid);
+        hipLaunchKernelGGL(span_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.fsum, L.fspans, w.foff, w.hdr + kHdrFacesOut, nullptr, invalid);
     }
     if ((rc = nm::check_launch("mesh simplify count kernels"))) return rc;
-    int64_t head[4] = {0, 0, 0, 0};                            // the one read-back: {K, F', n_invalid, first_invalid}
-    if ((rc = nm::check_hip(hipMemcpyAsync(head, w.hdr, sizeof(head), hipMemcpyDeviceToHost, st), "nm_mesh_simplify_count: read counts"))) return rc;
-    if ((rc = nm::check_hip(hipStreamSynchronize(st), "nm_mesh_simplify_count: sync"))) return rc;
-    NM_REQUIRE(head[kHdrInvalid] == 0, "nm_mesh_simplify_count: %lld invalid faces (an index outside [0, %lld)), the first of them face %lld",
-               (long long)head[kHdrInvalid], (long long)V, (long long)head[kHdrFirstInvalid]);
-    remember(Record{workspace, V, F, L.cells, head[kHdrClusters], head[kHdrFacesOut]});
+    int64_t head[4] = {0, 0, 0, 0};                            // the one read-back: {K, n_invalid, first_invalid, F'}
+    if ((rc = read_header("nm_mesh_simplify_count", w.hdr, head, 4, V, st))) return rc;
+    g_records.remember(Record{workspace, V, F, L.cells, head[kHdrClusters], head[kHdrFacesOut]});
     *n_clusters = head[kHdrClusters];
     *n_faces_out = head[kHdrFacesOut];
     return NM_OK;
@@ -685,7 +496,7 @@ int nm_mesh_simplify_fill(const float* verts, int64_t V, const int32_t* faces, i
     NM_REQUIRE(placement == kPlaceMean || placement == kPlaceQuadric, "nm_mesh_simplify_fill: placement = %d is neither 0 (mean) nor 1 (quadric)", placement);
     NM_REQUIRE(placement != kPlaceQuadric || (inc_off && (inc || F == 0)), "nm_mesh_simplify_fill: quadric placement needs inc_off and inc of nm_mesh_adjacency");
     const Layout L = layout_of(V, F, (int64_t)nx * ny * nz);
-    NM_SX_WORKSPACE("nm_mesh_simplify_fill");
+    NM_MESH_WORKSPACE("nm_mesh_simplify_fill", L.bytes);
     NM_REQUIRE(count_ok(n_clusters) && count_ok(n_faces_out), "nm_mesh_simplify_fill: bad counts %lld, %lld", (long long)n_clusters, (long long)n_faces_out);
     NM_REQUIRE((verts_out || n_clusters == 0) && (faces_out || n_faces_out == 0), "nm_mesh_simplify_fill: null output");      // (an empty tensor's pointer is null)
     {
@@ -695,7 +506,7 @@ int nm_mesh_simplify_fill(const float* verts, int64_t V, const int32_t* faces, i
         NM_REQUIRE(!any_overlap(outs, 3, ins, 5), "nm_mesh_simplify_fill: the outputs must not overlap each other, the mesh, the lists or the workspace");
     }
     Record r;
-    NM_REQUIRE(recall(workspace, &r) && r.V == V && r.F == F && r.cells == L.cells,
+    NM_REQUIRE(g_records.recall(workspace, &r) && r.V == V && r.F == F && r.cells == L.cells,
                "nm_mesh_simplify_fill: the workspace holds no count of this mesh and grid (run nm_mesh_simplify_count on it first)");
     NM_REQUIRE(r.n_clusters == n_clusters && r.n_faces_out == n_faces_out,
                "nm_mesh_simplify_fill: counts %lld clusters, %lld faces; nm_mesh_simplify_count left %lld, %lld in the workspace", (long long)n_clusters,
@@ -717,7 +528,7 @@ int nm_mesh_simplify_rows(const float* rows, int width, int64_t V, int64_t F, in
     NM_REQUIRE(width >= 1 && width <= 64, "nm_mesh_simplify_rows: width = %d must be in 1..64", width);
     NM_REQUIRE(rows || V == 0, "nm_mesh_simplify_rows: null rows");
     const Layout L = layout_of(V, F, (int64_t)nx * ny * nz);
-    NM_SX_WORKSPACE("nm_mesh_simplify_rows");
+    NM_MESH_WORKSPACE("nm_mesh_simplify_rows", L.bytes);
     NM_REQUIRE(count_ok(n_clusters) && n_clusters * width < (1ll << 31), "nm_mesh_simplify_rows: bad count %lld (n_clusters x width must be below 2^31)",
                (long long)n_clusters);
     NM_REQUIRE(out || n_clusters == 0, "nm_mesh_simplify_rows: null output");
@@ -726,7 +537,7 @@ int nm_mesh_simplify_rows(const float* rows, int width, int64_t V, int64_t F, in
         NM_REQUIRE(!any_overlap(outs, 1, ins, 2), "nm_mesh_simplify_rows: out must not overlap rows or the workspace");
     }
     Record r;
-    NM_REQUIRE(recall(workspace, &r) && r.V == V && r.F == F && r.cells == L.cells,
+    NM_REQUIRE(g_records.recall(workspace, &r) && r.V == V && r.F == F && r.cells == L.cells,
                "nm_mesh_simplify_rows: the workspace holds no count of this mesh and grid (run nm_mesh_simplify_count on it first)");
     NM_REQUIRE(r.n_clusters == n_clusters, "nm_mesh_simplify_rows: %lld clusters; nm_mesh_simplify_count left %lld in the workspace", (long long)n_clusters,
                (long long)r.n_clusters);

@@ -4,8 +4,8 @@
 // vertex_normals) smooths it without touching `faces`, and gives every posed frame of neuman_hip/mesh_pose.py the normals of its own geometry.
 //
 //   adjacency    count: every face range-checked BEFORE anything is indexed (invalid faces counted, their lowest index kept), a proper face adds
-//                one to each of its three vertices' counters.  scan: mesh_components.hip's shape -- a workgroup scans a span of kSpan counters,
-//                ONE workgroup scans the spans' sums, a last launch adds the span's offset: inc_off, and a copy of it as the fill's cursors.
+//                one to each of its three vertices' counters.  scan: mesh_device.h's span_rank_kernel over the counters and span_scan_kernel
+//                over the spans' sums, then a launch here adds the span's offset: inc_off, and a copy of it as the fill's cursors.
 //                fill: a proper face takes a slot of each of its vertices' lists through an integer atomicAdd on the cursor, so a list's ORDER
 //                depends on the interleaving; finish: a thread per vertex sorts its list in place (insertion up to kSortInThread entries, heap
 //                sort beyond: O(k log k), no second buffer), which makes the lists a function of the mesh alone.  The boundary flag comes from the
@@ -17,19 +17,15 @@
 //
 // Workspace: 4 bytes per vertex (counter, then cursor) + 24 bytes per face (six neighbour ids) + 16 bytes per kSpan vertices + 64.
 #include "common.h"
+#include "mesh_device.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr int kThreads = 256;                                 // every launch, the one-workgroup scan included
-constexpr int kSpan = 1024;                                   // counters one workgroup of the scan covers
-constexpr int kPerThread = kSpan / kThreads;                  // consecutive counters of one thread
-constexpr int kSortInThread = 32;                             // a segment of up to this many entries: insertion sort; longer: heap sort
-constexpr int64_t kHeaderBytes = 64;
-static_assert(kSpan % kThreads == 0 && kThreads % 64 == 0, "a span is whole threads' shares, a workgroup whole waves");
+using namespace nm_mesh;                                      // the sizes, the header's protocol, the scan, the sort, the checks: mesh_device.h
 
-enum { kHdrIncident = 0, kHdrInvalid = 1, kHdrFirstInvalid = 2 };      // int64 words of the header
+enum { kHdrIncident = 0 };                                    // int64 word of the header beside kHdrInvalid and kHdrFirstInvalid
 
 // ---- workspace --------------------------------------------------------------------------------------------------------------------------
 struct Layout {
@@ -37,11 +33,9 @@ struct Layout {
     int64_t off_sum, off_off, off_cursor, off_nbr, bytes;
 };
 
-inline int64_t up16(int64_t b) { return (b + 15) / 16 * 16; }
-
 inline Layout layout_of(int64_t V, int64_t F) {
     Layout L;
-    L.vspans = (V + kSpan - 1) / kSpan;
+    L.vspans = spans_of(V);
     L.off_sum = kHeaderBytes;
     L.off_off = L.off_sum + L.vspans * 8;
     L.off_cursor = up16(L.off_off + L.vspans * 8);
@@ -68,23 +62,14 @@ inline Work work_of(void* ws, const Layout& L) {
     return w;
 }
 
-inline unsigned blocks_for(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-__device__ __forceinline__ bool in_range(int32_t i, int64_t n) { return i >= 0 && (int64_t)i < n; }
-
 // ---- adjacency --------------------------------------------------------------------------------------------------------------------------
-__global__ void ms_reset_kernel(int64_t* __restrict__ hdr) {
-    if (threadIdx.x < 8) hdr[threadIdx.x] = threadIdx.x == kHdrFirstInvalid ? INT64_MAX : 0;
-}
-
 // rule S1: the range check comes before any use of an index; only a proper face counts.  `count` was zeroed by the call.
 __global__ void __launch_bounds__(kThreads) ms_count_kernel(const int32_t* __restrict__ faces, int64_t F, int64_t V, int32_t* count, int64_t* hdr) {
     const int64_t f = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (f >= F) return;
     const int32_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
     if (!(in_range(a, V) && in_range(b, V) && in_range(c, V))) {
-        atomicAdd(reinterpret_cast<unsigned long long*>(hdr + kHdrInvalid), 1ull);
-        atomicMin(reinterpret_cast<long long*>(hdr + kHdrFirstInvalid), (long long)f);
+        record_invalid_face(hdr, f);
         return;
     }
     if (a == b || a == c || b == c) return;
@@ -93,71 +78,7 @@ __global__ void __launch_bounds__(kThreads) ms_count_kernel(const int32_t* __res
     atomicAdd(count + c, 1);
 }
 
-// the exclusive scan of a span's counters inside the span -> inc_off, and the span's sum
-__global__ void __launch_bounds__(kThreads) ms_span_kernel(const int32_t* __restrict__ count, int64_t V, int32_t* __restrict__ inc_off,
-                                                           int64_t* __restrict__ span_sum, const int64_t* __restrict__ hdr) {
-    __shared__ int s_wave[kThreads / 64];
-    if (hdr[kHdrInvalid] != 0) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t first = (int64_t)blockIdx.x * kSpan + (int64_t)threadIdx.x * kPerThread;
-    int c[kPerThread], mine = 0;
-#pragma unroll
-    for (int r = 0; r < kPerThread; ++r) {
-        c[r] = first + r < V ? count[first + r] : 0;
-        mine += c[r];
-    }
-    int incl = mine;                                           // inclusive scan of the threads' shares across the wave
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();
-    int before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) {
-        const int n = s_wave[w];
-        before += w < wave ? n : 0;
-        total += n;
-    }
-    int run = before + incl - mine;
-#pragma unroll
-    for (int r = 0; r < kPerThread; ++r) {
-        if (first + r < V) inc_off[first + r] = run;
-        run += c[r];
-    }
-    if (threadIdx.x == 0) span_sum[blockIdx.x] = total;
-}
-
-// exclusive scan of the spans' sums by one workgroup (mesh_components.hip's mc_scan_kernel): the total -> the header and inc_off[V]
-__global__ void __launch_bounds__(kThreads) ms_scan_kernel(const int64_t* __restrict__ span_sum, int64_t spans, int64_t* __restrict__ span_off,
-                                                           int64_t* __restrict__ hdr, int32_t* __restrict__ inc_off, int64_t V) {
-    __shared__ int64_t part[kThreads];
-    if (hdr[kHdrInvalid] != 0) return;
-    const int64_t per = (spans + kThreads - 1) / kThreads, lo = threadIdx.x * per, hi = lo + per < spans ? lo + per : spans;
-    int64_t s = 0;
-    for (int64_t i = lo; i < hi; ++i) s += span_sum[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t run = 0;
-        for (int i = 0; i < kThreads; ++i) {
-            const int64_t t = part[i];
-            part[i] = run;
-            run += t;
-        }
-        hdr[kHdrIncident] = run;
-        inc_off[V] = (int32_t)run;                             // (at most 3F < 2^31)
-    }
-    __syncthreads();
-    int64_t run = part[threadIdx.x];
-    for (int64_t i = lo; i < hi; ++i) {
-        span_off[i] = run;
-        run += span_sum[i];
-    }
-}
-
+// after span_rank_kernel and span_scan_kernel: the in-span offset + the span's offset -> inc_off, and a copy as the fill's cursor
 __global__ void __launch_bounds__(kThreads) ms_offset_kernel(int64_t V, int32_t* __restrict__ inc_off, int32_t* __restrict__ cursor,
                                                              const int64_t* __restrict__ span_off, const int64_t* __restrict__ hdr) {
     if (hdr[kHdrInvalid] != 0) return;
@@ -182,51 +103,6 @@ __global__ void __launch_bounds__(kThreads) ms_fill_kernel(const int32_t* __rest
     for (int k = 0; k < 3; ++k) {
         const int64_t at = atomicAdd(cursor + v[k], 1);
         if (at >= 0 && at < 3 * F) inc[at] = (int32_t)f;
-    }
-}
-
-// ascending, in place, by one lane: insertion sort up to kSortInThread entries, heap sort beyond
-__device__ void sort_segment(int32_t* a, int n) {
-    if (n <= kSortInThread) {
-        for (int i = 1; i < n; ++i) {
-            const int32_t x = a[i];
-            int j = i;
-            while (j > 0 && a[j - 1] > x) {
-                a[j] = a[j - 1];
-                --j;
-            }
-            a[j] = x;
-        }
-        return;
-    }
-    for (int start = n / 2 - 1, end = n; end > 1;) {          // heap construction (start counts down to 0), then n - 1 extractions
-        int root;
-        int32_t x;
-        if (start >= 0) {
-            root = start--;
-            x = a[root];
-        } else {
-            --end;
-            x = a[end];
-            a[end] = a[0];
-            root = 0;
-        }
-        while (true) {                                         // sift x down from the hole at root, inside [0, end)
-            int child = 2 * root + 1;
-            if (child >= end) break;
-            int32_t cv = a[child];
-            if (child + 1 < end) {
-                const int32_t other = a[child + 1];
-                if (other > cv) {
-                    cv = other;
-                    ++child;
-                }
-            }
-            if (cv <= x) break;
-            a[root] = cv;
-            root = child;
-        }
-        a[root] = x;
     }
 }
 
@@ -337,14 +213,6 @@ __global__ void __launch_bounds__(kThreads) ms_normals_kernel(const float* __res
 }
 
 // ---- argument checks --------------------------------------------------------------------------------------------------------------------
-inline bool count_ok(int64_t n) { return n >= 0 && n < (1ll << 31); }
-inline bool mesh_ok(int64_t V, int64_t F) { return count_ok(V) && F >= 0 && F < (1ll << 31) && count_ok(3 * F); }
-
-inline bool overlap(const void* a, const void* b, int64_t bytes) {
-    const uintptr_t p = reinterpret_cast<uintptr_t>(a), q = reinterpret_cast<uintptr_t>(b);
-    return p < q + (uintptr_t)bytes && q < p + (uintptr_t)bytes;
-}
-
 #define NM_MS_MESH(who)                                                                                                                      \
     NM_REQUIRE(mesh_ok(V, F), who ": V = %lld, F = %lld: V and 3 F must be in [0, 2^31)", (long long)V, (long long)F);                      \
     NM_REQUIRE(faces || F == 0, who ": null faces")
@@ -369,19 +237,17 @@ int nm_mesh_adjacency(const int32_t* faces, int64_t F, int64_t V, int32_t* inc_o
     NM_MS_MESH("nm_mesh_adjacency");
     NM_MS_LISTS("nm_mesh_adjacency");
     NM_REQUIRE(n_incident, "nm_mesh_adjacency: null count pointer");
-    NM_REQUIRE(workspace, "nm_mesh_adjacency: null workspace");
-    NM_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "nm_mesh_adjacency: workspace must be 16-byte aligned");
-    NM_REQUIRE(workspace_bytes >= layout_of(V, F).bytes, "nm_mesh_adjacency: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
-               (long long)layout_of(V, F).bytes);
     const Layout L = layout_of(V, F);
+    NM_MESH_WORKSPACE("nm_mesh_adjacency", L.bytes);
     const Work w = work_of(workspace, L);
     hipStream_t st = nm::as_stream(stream);
     int rc = NM_OK;
     if (V > 0 && (rc = nm::check_hip(hipMemsetAsync(w.cursor, 0, (size_t)V * 4, st), "nm_mesh_adjacency: clear counters"))) return rc;
-    hipLaunchKernelGGL(ms_reset_kernel, dim3(1), dim3(64), 0, st, w.hdr);
+    hipLaunchKernelGGL(reset_header_kernel, dim3(1), dim3(64), 0, st, w.hdr);
     if (F > 0) hipLaunchKernelGGL(ms_count_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, faces, F, V, w.cursor, w.hdr);
-    if (V > 0) hipLaunchKernelGGL(ms_span_kernel, dim3((unsigned)L.vspans), dim3(kThreads), 0, st, w.cursor, V, inc_off, w.sum, w.hdr);
-    hipLaunchKernelGGL(ms_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.sum, L.vspans, w.off, w.hdr, inc_off, V);
+    if (V > 0)
+        hipLaunchKernelGGL(span_rank_kernel<Counters>, dim3((unsigned)L.vspans), dim3(kThreads), 0, st, Counters{w.cursor}, V, inc_off, 0, w.sum, w.hdr + kHdrInvalid);
+    hipLaunchKernelGGL(span_scan_kernel, dim3(1), dim3(kThreads), 0, st, w.sum, L.vspans, w.off, w.hdr + kHdrIncident, inc_off + V, w.hdr + kHdrInvalid);
     if (V > 0) {
         hipLaunchKernelGGL(ms_offset_kernel, dim3(blocks_for(V)), dim3(kThreads), 0, st, V, inc_off, w.cursor, w.off, w.hdr);
         if (F > 0) hipLaunchKernelGGL(ms_fill_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, faces, F, w.cursor, inc, w.hdr);
@@ -389,10 +255,7 @@ int nm_mesh_adjacency(const int32_t* faces, int64_t F, int64_t V, int32_t* inc_o
     }
     if ((rc = nm::check_launch("mesh adjacency kernels"))) return rc;
     int64_t head[3] = {0, 0, 0};                               // the one read-back: {n_incident, n_invalid, first_invalid}
-    if ((rc = nm::check_hip(hipMemcpyAsync(head, w.hdr, sizeof(head), hipMemcpyDeviceToHost, st), "nm_mesh_adjacency: read counts"))) return rc;
-    if ((rc = nm::check_hip(hipStreamSynchronize(st), "nm_mesh_adjacency: sync"))) return rc;
-    NM_REQUIRE(head[kHdrInvalid] == 0, "nm_mesh_adjacency: %lld invalid faces (an index outside [0, %lld)), the first of them face %lld",
-               (long long)head[kHdrInvalid], (long long)V, (long long)head[kHdrFirstInvalid]);
+    if ((rc = read_header("nm_mesh_adjacency", w.hdr, head, 3, V, st))) return rc;
     *n_incident = head[kHdrIncident];
     return NM_OK;
 }
@@ -407,7 +270,7 @@ int nm_mesh_smooth(const float* rows, int width, int64_t V, const int32_t* faces
     NM_MS_LISTS("nm_mesh_smooth");
     NM_REQUIRE(rows && out && scratch, "nm_mesh_smooth: null rows, out or scratch");
     const int64_t n = V * width, bytes = n * 4;
-    NM_REQUIRE(!overlap(rows, out, bytes) && !overlap(rows, scratch, bytes) && !overlap(out, scratch, bytes),
+    NM_REQUIRE(!overlap(rows, bytes, out, bytes) && !overlap(rows, bytes, scratch, bytes) && !overlap(out, bytes, scratch, bytes),
                "nm_mesh_smooth: rows, out and scratch must be three distinct buffers of V x width floats");
     hipStream_t st = nm::as_stream(stream);
     const int steps = mu != 0.f ? 2 : 1;
@@ -431,7 +294,7 @@ int nm_mesh_vertex_normals(const float* verts, int64_t B, int64_t V, const int32
     if (V == 0) return NM_OK;
     NM_MS_LISTS("nm_mesh_vertex_normals");
     NM_REQUIRE(verts && normals, "nm_mesh_vertex_normals: null verts or normals");
-    NM_REQUIRE(!overlap(verts, normals, B * V * 12), "nm_mesh_vertex_normals: verts and normals must be distinct buffers");
+    NM_REQUIRE(!overlap(verts, B * V * 12, normals, B * V * 12), "nm_mesh_vertex_normals: verts and normals must be distinct buffers");
     const unsigned frames = (unsigned)(B < 65535 ? B : 65535);
     hipLaunchKernelGGL(ms_normals_kernel, dim3(blocks_for(V), frames), dim3(kThreads), 0, nm::as_stream(stream), verts, B, V, faces, F, inc_off, inc, normals);
     return nm::check_launch("mesh vertex normals kernel");

@@ -1,4 +1,5 @@
-"""The sizes at which the mesh clean-up kernels (ml-neuman_amd/csrc/mesh_components.hip) change behaviour, and the meshes
+"""The sizes at which the mesh clean-up kernels (ml-neuman_amd/csrc/mesh_components.hip, and the ranking it
+takes from csrc/mesh_device.h) change behaviour, and the meshes
 tests/test_hip_mesh_components.py crosses them with.
 
 TABLE has the form of tests/helpers/mesh_sizes.py's: name -> (value, source file, pattern whose integer groups multiply to the value);
@@ -10,10 +11,10 @@ import numpy as np
 
 CSRC = 'ml-neuman_amd/csrc/'
 TABLE = {
-    # mc_span_kernel: a workgroup ranks kSpan items (vertices or faces), kSpan / kThreads rounds of kThreads
-    'SPAN': (1024, CSRC + 'mesh_components.hip', r'constexpr int kSpan = (\d+);'),
-    # mc_scan_kernel: ONE workgroup of kThreads scans the spans' sums, ceil(spans / kThreads) spans per thread
-    'THREADS': (256, CSRC + 'mesh_components.hip', r'constexpr int kThreads = (\d+);'),
+    # span_rank_kernel: a workgroup ranks kSpan items (vertices or faces), kSpan / kThreads consecutive ones per thread
+    'SPAN': (1024, CSRC + 'mesh_device.h', r'constexpr int kSpan = (\d+);'),
+    # span_scan_kernel: ONE workgroup of kThreads scans the spans' sums, ceil(spans / kThreads) spans per thread
+    'THREADS': (256, CSRC + 'mesh_device.h', r'constexpr int kThreads = (\d+);'),
 }
 C = types.SimpleNamespace(**{k: v[0] for k, v in TABLE.items()})
 

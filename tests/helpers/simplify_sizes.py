@@ -1,4 +1,5 @@
-"""The sizes at which the mesh simplification kernels (ml-neuman_amd/csrc/mesh_simplify.hip) change behaviour, and the meshes and grids
+"""The sizes at which the mesh simplification kernels (ml-neuman_amd/csrc/mesh_simplify.hip, and the scan and the sort it
+takes from csrc/mesh_device.h) change behaviour, and the meshes and grids
 tests/test_hip_mesh_simplify.py crosses them with.
 
 TABLE has the form of tests/helpers/mesh_sizes.py's: name -> (value, source file, pattern whose integer groups multiply to the value);
@@ -12,12 +13,12 @@ import smooth_sizes as SS
 
 CSRC = 'ml-neuman_amd/csrc/'
 TABLE = {
-    # sx_span_kernel: a workgroup scans kSpan counters (cells, clusters or faces), kSpan / kThreads consecutive ones per thread
-    'SPAN': (1024, CSRC + 'mesh_simplify.hip', r'constexpr int kSpan = (\d+);'),
-    # sx_scan_kernel: ONE workgroup of kThreads scans the spans' sums, ceil(spans / kThreads) spans per thread
-    'THREADS': (256, CSRC + 'mesh_simplify.hip', r'constexpr int kThreads = (\d+);'),
+    # span_rank_kernel: a workgroup scans kSpan counters (cells, clusters or faces), kSpan / kThreads consecutive ones per thread
+    'SPAN': (1024, CSRC + 'mesh_device.h', r'constexpr int kSpan = (\d+);'),
+    # span_scan_kernel: ONE workgroup of kThreads scans the spans' sums, ceil(spans / kThreads) spans per thread
+    'THREADS': (256, CSRC + 'mesh_device.h', r'constexpr int kThreads = (\d+);'),
     # sort_segment: a cluster of up to kSortInThread members by insertion, more by heap sort
-    'SORT': (32, CSRC + 'mesh_simplify.hip', r'constexpr int kSortInThread = (\d+);'),
+    'SORT': (32, CSRC + 'mesh_device.h', r'constexpr int kSortInThread = (\d+);'),
     # the duplicate table: kSlotsPerFace slots per input face; no bucket, so no threshold: what grows is the walk past taken slots
     'SLOTS': (2, CSRC + 'mesh_simplify.hip', r'constexpr int kSlotsPerFace = (\d+);'),
 }

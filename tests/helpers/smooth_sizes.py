@@ -1,4 +1,5 @@
-"""The sizes at which the mesh smoothing kernels (ml-neuman_amd/csrc/mesh_smooth.hip) change behaviour, and the meshes
+"""The sizes at which the mesh smoothing kernels (ml-neuman_amd/csrc/mesh_smooth.hip, and the scan and the sort it
+takes from csrc/mesh_device.h) change behaviour, and the meshes
 tests/test_hip_mesh_smooth.py crosses them with.
 
 TABLE has the form of tests/helpers/mesh_sizes.py's: name -> (value, source file, pattern whose integer groups multiply to the value);
@@ -10,12 +11,12 @@ import numpy as np
 
 CSRC = 'ml-neuman_amd/csrc/'
 TABLE = {
-    # ms_span_kernel: a workgroup scans kSpan counters, kSpan / kThreads consecutive ones per thread
-    'SPAN': (1024, CSRC + 'mesh_smooth.hip', r'constexpr int kSpan = (\d+);'),
-    # ms_scan_kernel: ONE workgroup of kThreads scans the spans' sums, ceil(spans / kThreads) spans per thread
-    'THREADS': (256, CSRC + 'mesh_smooth.hip', r'constexpr int kThreads = (\d+);'),
+    # span_rank_kernel: a workgroup scans kSpan counters, kSpan / kThreads consecutive ones per thread
+    'SPAN': (1024, CSRC + 'mesh_device.h', r'constexpr int kSpan = (\d+);'),
+    # span_scan_kernel: ONE workgroup of kThreads scans the spans' sums, ceil(spans / kThreads) spans per thread
+    'THREADS': (256, CSRC + 'mesh_device.h', r'constexpr int kThreads = (\d+);'),
     # sort_segment: up to kSortInThread entries by insertion, more by heap sort
-    'SORT': (32, CSRC + 'mesh_smooth.hip', r'constexpr int kSortInThread = (\d+);'),
+    'SORT': (32, CSRC + 'mesh_device.h', r'constexpr int kSortInThread = (\d+);'),
 }
 C = types.SimpleNamespace(**{k: v[0] for k, v in TABLE.items()})
 SEED = 31

@@ -38,9 +38,11 @@ def test_size_table_matches_the_source(name):
 
 def test_every_derived_size_is_past_its_threshold():
     C = CS.C
-    with open(os.path.join(ROOT, CS.TABLE['SPAN'][1])) as f:
-        src = f.read()
-    assert re.search(r'mc_scan_kernel, dim3\(1\), dim3\(kThreads\)', src) and not re.search(r'mc_scan_kernel, dim3\(1\), dim3\(\d', src)
+    src = ''
+    for path in (CS.TABLE['SPAN'][1], CS.CSRC + 'mesh_components.hip'):           # the shared header, then the file that launches its kernels
+        with open(os.path.join(ROOT, path)) as f:
+            src += f.read()
+    assert re.search(r'span_scan_kernel, dim3\(1\), dim3\(kThreads\)', src) and not re.search(r'span_scan_kernel, dim3\(1\), dim3\(\d', src)
     assert C.SPAN % C.THREADS == 0
     assert CS.PAST_ONE_SPAN == C.SPAN + 1 and CS.spans(CS.PAST_ONE_SPAN) == 2
     assert CS.PAST_THE_SCAN == C.SPAN * C.THREADS + 1 == 262145

@@ -46,9 +46,11 @@ def test_size_table_matches_the_source(name):
 
 def test_every_derived_size_is_past_its_threshold():
     C = SS.C
-    with open(os.path.join(ROOT, SS.TABLE['SPAN'][1])) as f:
-        src = f.read()
-    assert re.search(r'ms_scan_kernel, dim3\(1\), dim3\(kThreads\)', src) and not re.search(r'ms_scan_kernel, dim3\(1\), dim3\(\d', src)
+    src = ''
+    for path in (SS.TABLE['SPAN'][1], SS.CSRC + 'mesh_smooth.hip'):               # the shared header, then the file that launches its kernels
+        with open(os.path.join(ROOT, path)) as f:
+            src += f.read()
+    assert re.search(r'span_scan_kernel, dim3\(1\), dim3\(kThreads\)', src) and not re.search(r'span_scan_kernel, dim3\(1\), dim3\(\d', src)
     assert re.search(r'if \(n <= kSortInThread\)', src)                               # the threshold is inclusive: SORT entries are the last in-thread
     assert C.SPAN % C.THREADS == 0
     rows, cols = SS.GRID_SMALL
