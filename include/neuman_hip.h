@@ -899,6 +899,51 @@ int nm_raster_frames(nm_raster_t h, const float* verts, const double* w2c, const
                      float* zbuf, float* bary, nm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * mesh lattice -- per-face colour lattices ("mesh colours": colour nodes on a regular barycentric grid of every face; no UV
+ *   atlas, no seams, no packing) and the frame rasteriser that shades from them (csrc/mesh_lattice.hip, csrc/raster_device.h,
+ *   csrc/raster_frames.hip).  The reference has no such step.  A thinned mesh ('mesh simplify') keeps its shape but carries
+ *   one colour per vertex, so the look is sampled as sparsely as the geometry; a lattice holds more colour samples than the
+ *   mesh has vertices.  It belongs to the canonical mesh: baked once (neuman_hip/mesh_texture.py), it serves every frame of
+ *   every posed sequence.  tests/helpers/mesh_lattice_ref.py restates L1-L3 in numpy.
+ *   Every product, sum, difference and quotient below is a float32 operation rounded on its own, no fused multiply-add.
+ *     L1 nodes     resolution R, 1 <= R <= 64, the same for every face.  A face has S = (R+1)(R+2)/2 nodes (i1, i2) with
+ *                  i1, i2 >= 0, i1 + i2 <= R and i0 = R - i1 - i2; node (i1, i2) is stored at
+ *                  s = i2 (R+1) - i2 (i2-1)/2 + i1: rows run by i2, and row i2 has R + 1 - i2 entries.  The corners are the
+ *                  nodes (0, 0), (R, 0) and (0, R) of the face's vertices 0, 1 and 2.
+ *     L2 node rows nm_mesh_lattice_rows: out[f,s,:] = (w0 r0 + w1 r1) + w2 r2 with w_k = (float)i_k / (float)R (a correctly
+ *                  rounded division) and r_k the rows of face f's three vertices in `rows` [V,w], any w >= 1.  With the
+ *                  vertices as rows it gives the nodes' positions, with the vertex normals their (unnormalised) normals,
+ *                  with per-vertex colours a lattice that F2' shades as F2 shades the colours, up to rounding.  faces [F,3]
+ *                  DEVICE int32, rows [V,w] and out [F,S,w] DEVICE f32, sizes as int64_t, 1 <= V < 2^31, 1 <= 3 F < 2^31;
+ *                  every offset into out is 64-bit.  A face that names an index outside [0, V) is found on the device, is
+ *                  never dereferenced and none of its nodes is written; the entry then returns NM_ERR_ARG and nm_last_error()
+ *                  gives the number of such faces and the lowest such face index (rule C1's words).  One 24-byte read-back (a
+ *                  stream synchronise); the 64 bytes those words live in are allocated and freed by the call.
+ *     L3 lookup    at a point of face f with barycentrics (b0, b1, b2):  u1 = b1 (float)R, u2 = b2 (float)R;
+ *                  i1 = clamp(floorf(u1), 0, R-1), i2 = clamp(floorf(u2), 0, R-1-i1), as integers (a NaN counts as 0);
+ *                  f1 = u1 - i1, f2 = u2 - i2.  The UPPER sub-triangle of cell (i1, i2) is used iff f1 + f2 > 1 and
+ *                  i1 + i2 < R - 1 (a cell on the hypotenuse has no upper half, and a sum a rounding above 1 stays in
+ *                  the lower one): nodes a, b, c = (i1+1, i2+1), (i1, i2+1), (i1+1, i2) with weights
+ *                  ((f1 + f2) - 1, 1 - f1, 1 - f2).  Otherwise the LOWER one: nodes (i1, i2), (i1+1, i2), (i1, i2+1) with
+ *                  weights ((1 - f1) - f2, f1, f2).  Per channel c = (wa ca + wb cb) + wc cc.  The interpolant is
+ *                  piecewise linear and continuous over the face, so a few ulps of disagreement about the sub-triangle
+ *                  move the colour by a few ulps.  Every node read lies inside face f's S nodes whatever the barycentrics.
+ *     F2' colour   nm_raster_frames_lattice is nm_raster_frames with rule F2 replaced by L3 on face_colours [F,S,3] DEVICE
+ *                  f32 at the winning face and its b' (b1', b2').  Rules F1 and F3-F7 of 'mesh frames' hold word for word:
+ *                  face_id, zbuf and bary are the same bits as nm_raster_frames gives, the launches and the single 16-byte
+ *                  read-back are the same, and so is the handle's scratch; the lattice is the caller's (12 S F bytes).
+ *   Not here: export to OBJ with an atlas image; a resolution that varies from face to face; filtering under minification
+ *   (a face far smaller than a pixel shows one cell's blend, as a vertex-coloured face shows one point of its blend).
+ *   NM_ERR_ARG (with the entry's name in nm_last_error()) before any device work: nm_mesh_lattice_rows for a null pointer,
+ *   w < 1, R outside [1, 64], F < 1, V < 1 or a count of 2^31 or more; nm_raster_frames_lattice for everything
+ *   nm_raster_frames refuses, a null face_colours and R outside [1, 64].
+ * ------------------------------------------------------------------------------------------- */
+int nm_mesh_lattice_rows(const int32_t* faces, int64_t F, int64_t V, const float* rows, int w, int R, float* out, nm_stream_t stream);
+int nm_raster_frames_lattice(nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H,
+                             const float* face_colours, int R, const float* normals, const double* light, const uint8_t* bg, const float* bg_z,
+                             uint8_t* out, int32_t* face_id, float* zbuf, float* bary, nm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * isosurface -- a scalar field on a regular grid as an indexed triangle mesh (csrc/isosurface.hip).  The reference has
  *   no such step; it is what turns a trained density into geometry (neuman_hip/mesh_extract.py).  Marching tetrahedra
  *   on the Kuhn (Freudenthal) split of every cell: no 256-case table and no ambiguous case; the 16 cases of a

@@ -137,6 +137,26 @@ __device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
     x /= len; y /= len; z /= len;
 }
 
+// ---- colour lattice ('mesh lattice', rules L1 and L3) -----------------------------------------------------------------------------------
+// L1: where node (i1, i2) of a lattice of resolution R is stored: rows by i2, row i2 has R + 1 - i2 entries
+__device__ __forceinline__ int lattice_node(int R, int i1, int i2) { return i2 * (R + 1) - i2 * (i2 - 1) / 2 + i1; }
+
+// L3: the colour of a face's lattice (nodes [S,3]) at the barycentrics (., b1, b2).  The cell index is clamped while it is still a float: a
+// NaN falls into cell 0, and every node read lies inside the face's S nodes whatever b1 and b2 are
+__device__ __forceinline__ void lattice_colour(const float* __restrict__ nodes, int R, float b1, float b2, float c[3]) {
+    const float u1 = b1 * (float)R, u2 = b2 * (float)R;
+    const int i1 = (int)fminf(fmaxf(floorf(u1), 0.f), (float)(R - 1));
+    const int i2 = (int)fminf(fmaxf(floorf(u2), 0.f), (float)(R - 1 - i1));
+    const float f1 = u1 - (float)i1, f2 = u2 - (float)i2;
+    const bool upper = f1 + f2 > 1.f && i1 + i2 < R - 1;      // the hypotenuse cell has no upper half
+    const float wa = upper ? (f1 + f2) - 1.f : (1.f - f1) - f2, wb = upper ? 1.f - f1 : f1, wc = upper ? 1.f - f2 : f2;
+    const float* na = nodes + 3 * lattice_node(R, upper ? i1 + 1 : i1, upper ? i2 + 1 : i2);
+    const float* nb = nodes + 3 * lattice_node(R, upper ? i1 : i1 + 1, upper ? i2 + 1 : i2);
+    const float* nc = nodes + 3 * lattice_node(R, upper ? i1 + 1 : i1, upper ? i2 : i2 + 1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c[k] = (wa * na[k] + wb * nb[k]) + wc * nc[k];
+}
+
 }  // namespace nm_rast
 
 struct nm_raster_s {

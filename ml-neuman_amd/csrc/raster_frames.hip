@@ -16,6 +16,12 @@
 // No per-frame face records or boxes are kept: a record is nine of the twelve floats of the face's three screen vertices, so the tile kernel
 // reads those instead, and frame b's depth test sees the bits the one-frame kernel sees.  Scratch is 16 V bytes per frame, not 16 V + 64 F.
 // The order inside a (frame, tile) list is whatever the atomics made it; the minimum over (z, face id) does not depend on it.
+//
+// nm_raster_frames_lattice is the same call with rule F2 replaced by F2': the colour comes from the winning face's colour lattice ('mesh
+// lattice', rule L3; raster_device.h's lattice_colour) at the winner's barycentrics.  frames_tile_kernel is one body with the colour source as
+// a template argument; every other kernel and the host code serve both entries.  The lattice stays [F,S,3] as the caller made it: a pixel
+// reads three nodes of 12 bytes inside its face's 12 S bytes, neighbouring pixels of a face read the same or neighbouring nodes, so a wave's
+// nine loads fall into a few cache lines that the tile's other waves and the next frames' tiles find in L2.
 #include "raster_device.h"
 
 namespace {
@@ -27,6 +33,7 @@ constexpr int kScanThreads = 1024;           // the one workgroup of frames_scan
 struct Frames {
     int B, V, F, W, H, TX, T;
     int lit;                                 // normals and light were given
+    int R;                                   // the colour lattice's resolution (frames_tile_kernel<true>), else 0
     float light[3];                          // world space
 };
 
@@ -111,6 +118,8 @@ __device__ __forceinline__ void face_record(const float4* __restrict__ vs, const
 // rule F5's byte: truncation; fmaxf returns its other operand for a NaN, so a NaN gives 0
 __device__ __forceinline__ uint8_t colour_byte(float c) { return (uint8_t)fminf(fmaxf(c * 255.f, 0.f), 255.f); }
 
+// kLattice = false: `colours` is [V,3], rule F2 (null: white); true: `colours` is the faces' lattice [F,S,3] of resolution fr.R, rule F2'
+template <bool kLattice>
 __global__ void __launch_bounds__(kBatch) frames_tile_kernel(const float4* __restrict__ vscr, const int32_t* __restrict__ faces, const int64_t* __restrict__ offset,
                                                             const int32_t* __restrict__ list, const float* __restrict__ verts,
                                                             const float* __restrict__ colours, const float* __restrict__ normals, Frames fr,
@@ -158,7 +167,9 @@ __global__ void __launch_bounds__(kBatch) frames_tile_kernel(const float4* __res
     }
     const int i0 = faces[3 * fmin], i1 = faces[3 * fmin + 1], i2 = faces[3 * fmin + 2];
     float c[3] = {1.f, 1.f, 1.f};                               // F2: no colours is white itself, not a blend of ones
-    if (colours) {
+    if (kLattice) {                                            // F2': rule L3 at the winner's b'
+        lattice_colour(colours + (size_t)fmin * (size_t)(3 * ((fr.R + 1) * (fr.R + 2) / 2)), fr.R, b1, b2, c);
+    } else if (colours) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) c[k] = (b0 * colours[3 * i0 + k] + b1 * colours[3 * i1 + k]) + b2 * colours[3 * i2 + k];
     }
@@ -203,25 +214,22 @@ int reserve_frames(nm_raster_s* h, int B, int T) {
     return NM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int nm_raster_frames(nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H, const float* colours,
-                     const float* normals, const double* light, const uint8_t* bg, const float* bg_z, uint8_t* out, int32_t* face_id, float* zbuf,
-                     float* bary, nm_stream_t stream) {
-    NM_REQUIRE(h && verts && w2c && intr && out, "nm_raster_frames: null pointer");
-    NM_REQUIRE(B >= 1 && B <= 65535, "nm_raster_frames: B = %d frames (1 <= B <= 65535)", B);
-    NM_REQUIRE(W >= 1 && H >= 1 && (int64_t)W * H <= (1ll << 30), "nm_raster_frames: bad image size W=%d H=%d", W, H);
-    NM_REQUIRE((normals != nullptr) == (light != nullptr), "nm_raster_frames: normals and light go together (normals %s, light %s)",
-               normals ? "given" : "null", light ? "given" : "null");
-    NM_REQUIRE(!light || (isfinite(light[0]) && isfinite(light[1]) && isfinite(light[2])), "nm_raster_frames: a non-finite light");
+// both entries: R = 0 is nm_raster_frames (colours [V,3], nullable), R >= 1 nm_raster_frames_lattice (colours [F,S,3])
+int raster_frames(const char* who, nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H, const float* colours, int R,
+                  const float* normals, const double* light, const uint8_t* bg, const float* bg_z, uint8_t* out, int32_t* face_id, float* zbuf,
+                  float* bary, nm_stream_t stream) {
+    NM_REQUIRE(B >= 1 && B <= 65535, "%s: B = %d frames (1 <= B <= 65535)", who, B);
+    NM_REQUIRE(W >= 1 && H >= 1 && (int64_t)W * H <= (1ll << 30), "%s: bad image size W=%d H=%d", who, W, H);
+    NM_REQUIRE((normals != nullptr) == (light != nullptr), "%s: normals and light go together (normals %s, light %s)", who, normals ? "given" : "null",
+               light ? "given" : "null");
+    NM_REQUIRE(!light || (isfinite(light[0]) && isfinite(light[1]) && isfinite(light[2])), "%s: a non-finite light", who);
     hipStream_t st = nm::as_stream(stream);
     Frames fr = {};
     fr.B = B; fr.V = h->V; fr.F = h->F; fr.W = W; fr.H = H;
     fr.TX = (W + kTile - 1) / kTile;
     fr.T = fr.TX * ((H + kTile - 1) / kTile);
     fr.lit = normals ? 1 : 0;
+    fr.R = R;
     for (int k = 0; k < 3; ++k) fr.light[k] = light ? (float)light[k] : 0.f;
     const int64_t n = (int64_t)B * fr.T;
     int rc = NM_OK;
@@ -239,15 +247,38 @@ int nm_raster_frames(nm_raster_t h, const float* verts, const double* w2c, const
     if ((rc = nm::check_hip(hipStreamSynchronize(st), "nm_raster_frames: sync"))) return rc;
     const int64_t total = back[0];
     if (total < 0 || (total + n - 1) / n > h->F) {                 // (total > n F, without the product)
-        nm::set_error("nm_raster_frames: bad list total %lld", (long long)total); return NM_ERR_UNSUPPORTED; }
+        nm::set_error("%s: bad list total %lld", who, (long long)total); return NM_ERR_UNSUPPORTED; }
     if ((rc = reserve_lists(h, total))) return rc;
     if (total > 0) hipLaunchKernelGGL(frames_bin_kernel<true>, per_face, dim3(256), 0, st, h->d_fvscr, h->d_faces, fr, h->d_fcount, h->d_foffset, h->d_list, total);
-    hipLaunchKernelGGL(frames_tile_kernel, dim3(fr.T, B), dim3(kBatch), 0, st, h->d_fvscr, h->d_faces, h->d_foffset, h->d_list, verts, colours, normals, fr, bg,
-                       bg_z, out, face_id, zbuf, bary);
+    if (R > 0)
+        hipLaunchKernelGGL(frames_tile_kernel<true>, dim3(fr.T, B), dim3(kBatch), 0, st, h->d_fvscr, h->d_faces, h->d_foffset, h->d_list, verts, colours, normals, fr,
+                           bg, bg_z, out, face_id, zbuf, bary);
+    else
+        hipLaunchKernelGGL(frames_tile_kernel<false>, dim3(fr.T, B), dim3(kBatch), 0, st, h->d_fvscr, h->d_faces, h->d_foffset, h->d_list, verts, colours, normals, fr,
+                           bg, bg_z, out, face_id, zbuf, bary);
     if ((rc = nm::check_launch("nm_raster_frames: frames_tile_kernel"))) return rc;
     // (the bad frame's outputs are defined all the same: its lists are empty, so face_id -1, zbuf +inf and out the background)
-    NM_REQUIRE(back[1] == 0, "nm_raster_frames: a non-finite w2c or intrinsic entry in frame %lld", (long long)(back[1] - 1));
+    NM_REQUIRE(back[1] == 0, "%s: a non-finite w2c or intrinsic entry in frame %lld", who, (long long)(back[1] - 1));
     return NM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nm_raster_frames(nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H, const float* colours,
+                     const float* normals, const double* light, const uint8_t* bg, const float* bg_z, uint8_t* out, int32_t* face_id, float* zbuf,
+                     float* bary, nm_stream_t stream) {
+    NM_REQUIRE(h && verts && w2c && intr && out, "nm_raster_frames: null pointer");
+    return raster_frames("nm_raster_frames", h, verts, w2c, intr, B, W, H, colours, 0, normals, light, bg, bg_z, out, face_id, zbuf, bary, stream);
+}
+
+int nm_raster_frames_lattice(nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H, const float* face_colours,
+                             int R, const float* normals, const double* light, const uint8_t* bg, const float* bg_z, uint8_t* out, int32_t* face_id,
+                             float* zbuf, float* bary, nm_stream_t stream) {
+    NM_REQUIRE(h && verts && w2c && intr && out && face_colours, "nm_raster_frames_lattice: null pointer");
+    NM_REQUIRE(R >= 1 && R <= 64, "nm_raster_frames_lattice: R = %d (1 <= R <= 64)", R);
+    return raster_frames("nm_raster_frames_lattice", h, verts, w2c, intr, B, W, H, face_colours, R, normals, light, bg, bg_z, out, face_id, zbuf, bary, stream);
 }
 
 }  // extern "C"

@@ -179,15 +179,21 @@ class Rasterizer:
                        "nm_raster_silhouette_backward_batch")
         return g_verts
 
-    def render_frames(self, verts, cameras, colours=None, normals=None, light=LIGHT, background=None, background_z=None, want_geometry=False, out=None):
+    def render_frames(self, verts, cameras, colours=None, normals=None, light=LIGHT, background=None, background_z=None, want_geometry=False, out=None, *,
+                      face_colours=None):
         """nm_raster_frames (the header's 'mesh frames', rules F1-F7): B frames of the mesh as images, one call and one host read -> out uint8
         [B,H,W,3], or (out, face_id [B,H,W] int32, zbuf [B,H,W] f32, bary [B,H,W,3] f32) with want_geometry; frame b's geometry is the bits
         `rasterize` gives on frame b.  verts [B,V,3]; `cameras` as `batch_cameras` makes them; colours [V,3] f32 (None: white); normals
         [B,V,3] f32 switch the diffuse light at `light` on; background uint8 [B,H,W,3] (None: white); background_z f32 [B,H,W], camera-space
-        depth the mesh must be nearer than.  `out`: a dense uint8 [B,H,W,3] tensor on verts' device to write into instead of a new one."""
+        depth the mesh must be nearer than.  `out`: a dense uint8 [B,H,W,3] tensor on verts' device to write into instead of a new one.
+        face_colours [F,S,3] f32, a colour lattice as `mesh_texture.bake_face_colours` makes it, in place of `colours` (ValueError for both):
+        nm_raster_frames_lattice (the header's 'mesh lattice', rule F2'), the resolution recovered from S; the geometry is the same bits."""
         who = "render_frames"
+        if colours is not None and face_colours is not None:
+            raise ValueError(f"{who}: give colours (one per vertex) or face_colours (a lattice per face), not both")
         verts, w2c, intr, B, W, H = self._batch(verts, cameras, who)
         dev = verts.device
+        R = None if face_colours is None else lattice_resolution_of(face_colours, self.F, who)
 
         def dense(t, name, dtype, shape):
             if t is None:
@@ -199,6 +205,7 @@ class Rasterizer:
             return t.detach().contiguous()
 
         colours = dense(colours, "colours", torch.float32, (self.V, 3))
+        face_colours = dense(face_colours, "face_colours", torch.float32, tuple(getattr(face_colours, 'shape', ())))
         normals = dense(normals, "normals", torch.float32, (B, self.V, 3))
         background = dense(background, "background", torch.uint8, (B, H, W, 3))
         background_z = dense(background_z, "background_z", torch.float32, (B, H, W))
@@ -213,11 +220,25 @@ class Rasterizer:
             face_id = torch.empty((B, H, W), device=dev, dtype=torch.int32) if want_geometry else None
             zbuf = torch.empty((B, H, W), device=dev, dtype=torch.float32) if want_geometry else None
             bary = torch.empty((B, H, W, 3), device=dev, dtype=torch.float32) if want_geometry else None
-            _lib.check(_lib.lib().nm_raster_frames(self._h, _lib.dev_ptr(verts), _lib.dev_ptr(w2c, torch.float64), _lib.dev_ptr(intr, torch.float64), B, W, H,
-                                                   _lib.dev_ptr(colours), _lib.dev_ptr(normals), light_p, _lib.dev_ptr(background, torch.uint8),
-                                                   _lib.dev_ptr(background_z), _lib.dev_ptr(out, torch.uint8), _lib.dev_ptr(face_id, torch.int32),
-                                                   _lib.dev_ptr(zbuf), _lib.dev_ptr(bary), _lib.stream_ptr()), "nm_raster_frames")
+            head = (self._h, _lib.dev_ptr(verts), _lib.dev_ptr(w2c, torch.float64), _lib.dev_ptr(intr, torch.float64), B, W, H)
+            tail = (_lib.dev_ptr(normals), light_p, _lib.dev_ptr(background, torch.uint8), _lib.dev_ptr(background_z), _lib.dev_ptr(out, torch.uint8),
+                    _lib.dev_ptr(face_id, torch.int32), _lib.dev_ptr(zbuf), _lib.dev_ptr(bary), _lib.stream_ptr())
+            if face_colours is None:
+                _lib.check(_lib.lib().nm_raster_frames(*head, _lib.dev_ptr(colours), *tail), "nm_raster_frames")
+            else:
+                _lib.check(_lib.lib().nm_raster_frames_lattice(*head, _lib.dev_ptr(face_colours), R, *tail), "nm_raster_frames_lattice")
         return (out, face_id, zbuf, bary) if want_geometry else out
+
+
+def lattice_resolution_of(face_colours, n_faces, who):
+    """R of a colour lattice [F,S,3] with S = (R+1)(R+2)/2 nodes per face (the header's 'mesh lattice', rule L1), 1 <= R <= 64; NeumanHipError
+    for any other shape"""
+    shape = tuple(getattr(face_colours, 'shape', ()))
+    if len(shape) == 3 and shape[0] == n_faces and shape[2] == 3:
+        R = (math.isqrt(8 * int(shape[1]) + 1) - 3) // 2
+        if 1 <= R <= 64 and (R + 1) * (R + 2) // 2 == shape[1]:
+            return R
+    raise _lib.NeumanHipError(f"{who}: face_colours must be [{n_faces}, S, 3] with S = (R+1)(R+2)/2 nodes for a resolution 1 <= R <= 64, got {list(shape)}")
 
 
 def batch_cameras(caps, device):
