@@ -932,7 +932,7 @@ int nm_raster_frames(nm_raster_t h, const float* verts, const double* w2c, const
  *                  f32 at the winning face and its b' (b1', b2').  Rules F1 and F3-F7 of 'mesh frames' hold word for word:
  *                  face_id, zbuf and bary are the same bits as nm_raster_frames gives, the launches and the single 16-byte
  *                  read-back are the same, and so is the handle's scratch; the lattice is the caller's (12 S F bytes).
- *   Not here: export to OBJ with an atlas image; a resolution that varies from face to face; filtering under minification
+ *   Not here ('mesh atlas' exports to OBJ): a resolution that varies from face to face; filtering under minification
  *   (a face far smaller than a pixel shows one cell's blend, as a vertex-coloured face shows one point of its blend).
  *   NM_ERR_ARG (with the entry's name in nm_last_error()) before any device work: nm_mesh_lattice_rows for a null pointer,
  *   w < 1, R outside [1, 64], F < 1, V < 1 or a count of 2^31 or more; nm_raster_frames_lattice for everything
@@ -942,6 +942,54 @@ int nm_mesh_lattice_rows(const int32_t* faces, int64_t F, int64_t V, const float
 int nm_raster_frames_lattice(nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H,
                              const float* face_colours, int R, const float* normals, const double* light, const uint8_t* bg, const float* bg_z,
                              uint8_t* out, int32_t* face_id, float* zbuf, float* bary, nm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * mesh atlas -- a texture atlas packed from the colour lattices of 'mesh lattice', so that a lattice-coloured mesh can leave
+ *   the project as an OBJ with one image (csrc/mesh_atlas.hip, neuman_hip/mesh_export.py).  The reference has no such step.
+ *   Two faces share a block of texels; the nodes of a face are texels, and the gutter between the two faces is filled so
+ *   that a viewer's bilinear filter shows rule L3's blend in the cells on the hypotenuse.
+ *   tests/helpers/mesh_atlas_ref.py restates A1-A5 in numpy.  As in 'mesh lattice' every product, sum and difference is a
+ *   float32 operation rounded on its own, no fused multiply-add; every offset is 64-bit.  S = (R+1)(R+2)/2 and node
+ *   (i1, i2) sits at the index rule L1 gives it.
+ *     A1 size      nm_mesh_atlas_size, HOST only, no device work.  A block is BW = R+4 texels wide and BH = R+1 high; faces
+ *                  2p and 2p+1 share block p, P = ceil(F/2) blocks.  nbx = the smallest n >= 1 with n n BW >= P BH (integer
+ *                  arithmetic only: the atlas is about square), nby = ceil(P / nbx), W = nbx BW, H = nby BH.  Block p starts
+ *                  at x0 = (p mod nbx) BW, y0 = (p div nbx) BH.  E.g. (F, R) = (13776, 8) gives 864 x 864 with nbx = 72,
+ *                  (600, 8) 180 x 180, (10, 5) 18 x 18, (1, 1) 5 x 2.
+ *     A2 texels    in block-local (x, y), 0 <= x < BW, 0 <= y < BH: node (i1, i2) of the even ("lower") face sits at
+ *                  (i1, i2); the odd ("upper") face is the same picture under the point reflection (x, y) -> (R+3-x, R-y).
+ *                  Lower nodes have x + y <= R, upper nodes x + y >= R+3; the diagonals x + y = R+1 and x + y = R+2 are the
+ *                  lower and the upper face's gutters.  Every texel of a block belongs to exactly one of the four sets.
+ *     A3 values    nm_mesh_atlas_pack: face_colours [F,S,3] -> atlas [H,W,3], both DEVICE f32, row 0 first.  One thread per
+ *                  texel, gather form: every texel of the atlas is written exactly once; no memset, no atomic, no
+ *                  read-back.  In a face's own (unreflected) local coordinates: a node texel is a bit copy of its node; a
+ *                  gutter texel (x, y) with x + y = R+1 and 1 <= x <= R is (c(x, y-1) + c(x-1, y)) - c(x-1, y-1); the
+ *                  gutter texel (R+1, 0) is a copy of node (R, 0); the upper half of the last block when F is odd and the
+ *                  blocks p >= P of the last row are +0.0.  A NaN node gives a NaN texel and a NaN in each gutter texel
+ *                  computed from it, nothing else.  The values are not clamped: the byte egress (nm_frame_to_uint8) clamps.
+ *     A4 uv        corner k of face f is node (0, 0), (R, 0) or (0, R); its texture coordinate is the centre of that node's
+ *                  texel (X, Y): u = (X + 0.5) / W, v = 1 - (Y + 0.5) / H in float64 (image row 0 is the top row, as OBJ
+ *                  viewers expect).  No two faces share a coordinate.  No entry point: neuman_hip.mesh_export.atlas_uvs.
+ *     A5 sample    nm_mesh_atlas_sample: what a viewer with bilinear filtering shows at a point of face f with barycentrics
+ *                  (b0, b1, b2).  The cell is L3's: u1 = b1 (float)R, u2 = b2 (float)R; i1 = clamp(floorf(u1), 0, R-1),
+ *                  i2 = clamp(floorf(u2), 0, R-1-i1) (a NaN counts as 0); f1 = u1 - i1, f2 = u2 - i2.  Per channel
+ *                  c = ((1-f1)(1-f2) t00 + f1 (1-f2) t10) + ((1-f1) f2 t01 + f1 f2 t11), each weight ONE product of two
+ *                  rounded factors, t_ab the texel at local (i1+a, i2+b) of the face's half block (reflected for an odd
+ *                  face).  face_id [n] DEVICE int32, bary [n,3] and out [n,3] DEVICE f32: exactly the face_id and bary
+ *                  nm_raster_frames returns, so a textured view is that call followed by this one.  A face_id outside
+ *                  [0, F) gives (0, 0, 0) and reads nothing; whatever the barycentrics, every read lies inside the face's
+ *                  own half block.  One thread per point, no read-back.
+ *   Derived: at a node's barycentrics the sample is the node.  With D = t00 - t10 - t01 + t11 the sample is L3's value plus
+ *   f1 f2 D in a cell's lower sub-triangle and plus (1-f1)(1-f2) D in its upper one, at most |D| / 4 in magnitude; in a
+ *   cell on the hypotenuse A3's gutter makes D vanish (up to its own rounding), so there the sample is L3's value.
+ *   Not here: a textured colour source inside nm_raster_frames; padding for mip-mapped viewers; glTF.
+ *   NM_ERR_ARG (with the entry's name in nm_last_error()) before any device work: a null pointer, F < 1, R outside
+ *   [1, 64], W or H above 16384 (e.g. F = 2^20 at R = 64), and for nm_mesh_atlas_sample n < 1.
+ * ------------------------------------------------------------------------------------------- */
+int nm_mesh_atlas_size(int64_t F, int R, int* W, int* H, int* nbx);
+int nm_mesh_atlas_pack(const float* face_colours, int64_t F, int R, float* atlas, nm_stream_t stream);
+int nm_mesh_atlas_sample(const float* atlas, int64_t F, int R, const int32_t* face_id, const float* bary, int64_t n, float* out,
+                         nm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * isosurface -- a scalar field on a regular grid as an indexed triangle mesh (csrc/isosurface.hip).  The reference has

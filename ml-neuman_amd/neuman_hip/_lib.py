@@ -227,6 +227,9 @@ SIGNATURES = {
     "nm_mesh_lattice_rows": (i32, [c_i32p, i64, i64, c_f32p, i32, i32, c_f32p, c_stream]),
     "nm_raster_frames_lattice": (i32, [ctypes.c_void_p, c_f32p, ctypes.c_void_p, ctypes.c_void_p, i32, i32, i32, c_f32p, i32, c_f32p,
                                        ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, c_f32p, ctypes.c_void_p, c_i32p, c_f32p, c_f32p, c_stream]),
+    "nm_mesh_atlas_size": (i32, [i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+    "nm_mesh_atlas_pack": (i32, [c_f32p, i64, i32, c_f32p, c_stream]),
+    "nm_mesh_atlas_sample": (i32, [c_f32p, i64, i32, c_i32p, c_f32p, i64, c_f32p, c_stream]),
     "nm_isosurface_workspace_bytes": (i64, [i32, i32, i32]),
     "nm_isosurface_count": (i32, [c_f32p, i32, i32, i32, ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_void_p, i64, ctypes.POINTER(i64),
                                   ctypes.POINTER(i64), c_stream]),

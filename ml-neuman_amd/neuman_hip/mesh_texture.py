@@ -13,7 +13,7 @@ sequence.
     face_colours = bake_face_colours(net, verts, faces, normals, R)         # [F,S,3]: the net asked at every node
     frames = render_mesh_frames(posed, faces, caps, normals=posed_normals, face_colours=face_colours)
 
-Not here: export to OBJ with an atlas image, a resolution that varies from face to face, filtering under minification.  Every tensor is a
+Not here (mesh_export.py writes the OBJ): a resolution that varies from face to face, filtering under minification.  Every tensor is a
 CUDA tensor; there is no CPU path."""
 import math
 
