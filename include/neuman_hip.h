@@ -932,8 +932,9 @@ int nm_raster_frames(nm_raster_t h, const float* verts, const double* w2c, const
  *                  f32 at the winning face and its b' (b1', b2').  Rules F1 and F3-F7 of 'mesh frames' hold word for word:
  *                  face_id, zbuf and bary are the same bits as nm_raster_frames gives, the launches and the single 16-byte
  *                  read-back are the same, and so is the handle's scratch; the lattice is the caller's (12 S F bytes).
- *   Not here ('mesh atlas' exports to OBJ): a resolution that varies from face to face; filtering under minification
- *   (a face far smaller than a pixel shows one cell's blend, as a vertex-coloured face shows one point of its blend).
+ *   Not here ('mesh atlas' exports to OBJ, 'mesh mip' filters under minification: with rule F2' alone a face far smaller
+ *   than a pixel shows one cell's blend, as a vertex-coloured face shows one point of its blend): a resolution that varies
+ *   from face to face.
  *   NM_ERR_ARG (with the entry's name in nm_last_error()) before any device work: nm_mesh_lattice_rows for a null pointer,
  *   w < 1, R outside [1, 64], F < 1, V < 1 or a count of 2^31 or more; nm_raster_frames_lattice for everything
  *   nm_raster_frames refuses, a null face_colours and R outside [1, 64].
@@ -942,6 +943,60 @@ int nm_mesh_lattice_rows(const int32_t* faces, int64_t F, int64_t V, const float
 int nm_raster_frames_lattice(nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H,
                              const float* face_colours, int R, const float* normals, const double* light, const uint8_t* bg, const float* bg_z,
                              uint8_t* out, int32_t* face_id, float* zbuf, float* bary, nm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * mesh mip -- a pyramid of the colour lattices of 'mesh lattice' and the frame rasteriser that filters with it under
+ *   minification (csrc/mesh_lattice.hip, csrc/raster_device.h, csrc/raster_frames.hip).  The reference has no such step.
+ *   One R serves the whole mesh, so short faces are over-resolved, and a far camera draws faces two or three pixels wide whose
+ *   R = 8 lattice has nine nodes along an edge; rule L3 point-samples that lattice at the pixel centre, which shows as moire
+ *   within a frame and as shimmer from frame to frame.  tests/helpers/mesh_mip_ref.py restates M1-M3 in numpy.  As in 'mesh
+ *   lattice' every product, sum, difference and quotient is a float32 operation rounded on its own, no fused multiply-add;
+ *   sqrtf is the correctly rounded one.
+ *     M1 pyramid   a lattice [F,S(R0),w] has levels l = 0 .. with resolution R_l = R0 >> l while 2^l divides R0: at most
+ *                  1 + (the trailing zero bits of R0) levels -- 4 for R0 = 8, 1 for an odd R0, 7 for R0 = 64.  The pyramid
+ *                  is one f32 buffer, level-major: level l is a contiguous [F,S(R_l),w] block after the blocks of the finer
+ *                  levels, level 0 the input byte for byte.  nm_mesh_lattice_pyramid_size (HOST only) gives the sum of
+ *                  S(R_l) over the levels, so the buffer holds F w times that many floats.  Coarse node (i1, i2) of level
+ *                  l+1 sits on fine node (2 i1, 2 i2) of level l, value c, and is
+ *                    a corner (two of i0, i1, i2 zero)    c, copied;
+ *                    an edge node (exactly one zero)      0.5 c + 0.25 (a + b), a and b the two fine neighbours along that
+ *                                                         edge, a the one with the smaller i1 (on the edge i1 = 0: the
+ *                                                         smaller i2);
+ *                    interior                             0.25 c + 0.125 (((((n0 + n1) + n2) + n3) + n4) + n5) over the six
+ *                                                         fine neighbours at (+1,0), (0,+1), (-1,+1), (-1,0), (0,-1), (+1,-1)
+ *                                                         in (i1, i2), which all exist.
+ *                  These weights are the transpose of linear prolongation on the triangular lattice (restricted to the edge
+ *                  on an edge): a linear lattice stays linear at every level.  Edge and corner values depend on nodes of
+ *                  that edge alone, so two faces whose shared-edge nodes agree at level 0 agree there at every level: no
+ *                  seam is added.  nm_mesh_lattice_pyramid: lattice and out DEVICE f32; lattice == out is the in-place form
+ *                  (level 0 is already in out), otherwise the two must not overlap and level 0 is copied on the stream.
+ *                  One launch per coarser level, one thread per coarse node, every node written once; no read-back, no
+ *                  workspace.  1 <= w <= 64.
+ *     M2 level     one value per frame and face, computed at the pixel from the winner's screen vertices (x0,y0), (x1,y1),
+ *                  (x2,y2) (rule 1's u, v as floats): d01 = v1 - v0, d02 = v2 - v0, d12 = v2 - v1;
+ *                  e2 = max(max(|d01|^2, |d02|^2), |d12|^2) with |d|^2 = dx dx + dy dy; cr = |d01.x d02.y - d01.y d02.x|;
+ *                  rho = ((lod_scale (float)R0) sqrtf(e2)) / cr: the level-0 nodes per pixel across the face's narrowest
+ *                  extent under an affine approximation (perspective inside a face is ignored).  l = 0; while rho >= 2 and
+ *                  l < levels - 1: rho *= 0.5, ++l.  t = (l < levels - 1) ? fminf(fmaxf(rho - 1, 0), 1) : 0.  A NaN rho gives
+ *                  l = 0, t = 0 (fmaxf returns its other operand); an infinite one the coarsest level.
+ *     M3 colour    c = L3 on level l of face f at (b1', b2'); if t > 0, c = c + t (L3 on level l+1 - c) per channel.  With
+ *                  t == 0 the second lookup is skipped and c is L3's own bits on that level.
+ *     F2'' colour  nm_raster_frames_lattice_mip is nm_raster_frames_lattice with rule F2' replaced by M2 and M3 on pyramid
+ *                  [levels][F,S(R_l),3].  Rules F1 and F3-F7 hold word for word: the same geometry bits, launches, single
+ *                  16-byte read-back and scratch.  lod_scale = 0 is nm_raster_frames_lattice on level 0; a huge one is
+ *                  nm_raster_frames_lattice on the coarsest level.
+ *   Not here: filtering the corner nodes across the faces around a vertex (they stay point samples, as per-vertex colours
+ *   are); a level that varies inside a face, anisotropic filtering; atlas padding for mip-mapping viewers; a per-face R.
+ *   NM_ERR_ARG (with the entry's name in nm_last_error()) before any device work: a null pointer, R0 outside [1, 64], levels
+ *   < 1 or more than R0 allows, w outside [1, 64], F < 1 or 3 F >= 2^31; nm_raster_frames_lattice_mip for everything
+ *   nm_raster_frames refuses, a null pyramid and a lod_scale that is negative or not finite.
+ * ------------------------------------------------------------------------------------------- */
+int nm_mesh_lattice_pyramid_size(int R0, int levels, int64_t* nodes_per_face_total);
+int nm_mesh_lattice_pyramid(const float* lattice, int64_t F, int R0, int levels, int w, float* out, nm_stream_t stream);
+int nm_raster_frames_lattice_mip(nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H,
+                                 const float* pyramid, int R0, int levels, float lod_scale, const float* normals, const double* light,
+                                 const uint8_t* bg, const float* bg_z, uint8_t* out, int32_t* face_id, float* zbuf, float* bary,
+                                 nm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * mesh atlas -- a texture atlas packed from the colour lattices of 'mesh lattice', so that a lattice-coloured mesh can leave

@@ -157,6 +157,45 @@ __device__ __forceinline__ void lattice_colour(const float* __restrict__ nodes, 
     for (int k = 0; k < 3; ++k) c[k] = (wa * na[k] + wb * nb[k]) + wc * nc[k];
 }
 
+// ---- lattice pyramid ('mesh mip', rules M2 and M3) --------------------------------------------------------------------------------------
+// where level l's block of a pyramid of resolution R0 starts, in nodes per face: S(R0 >> k) summed over the finer levels k < l
+__device__ __forceinline__ int pyramid_nodes_before(int R0, int l) {
+    int n = 0;
+    for (int k = 0; k < l; ++k) n += ((R0 >> k) + 1) * ((R0 >> k) + 2) / 2;
+    return n;
+}
+
+// M2: the level of a face from its screen vertices r0 = (x0, y0, x1, y1), r1 = (x2, y2, ., .) and the blend t towards the next coarser
+// one.  rho is the number of level-0 nodes per pixel across the face's narrowest extent (twice its area over its longest edge).  A NaN rho
+// fails the loop's comparison and fmaxf returns its other operand for it: l = 0, t = 0; an infinite one walks to the coarsest level
+__device__ __forceinline__ int lattice_level(const float4 r0, const float4 r1, int R0, int levels, float lod_scale, float& t) {
+    const float ax = r0.z - r0.x, ay = r0.w - r0.y;           // d01
+    const float bx = r1.x - r0.x, by = r1.y - r0.y;           // d02
+    const float cx = r1.x - r0.z, cy = r1.y - r0.w;           // d12
+    const float e2 = fmaxf(fmaxf(ax * ax + ay * ay, bx * bx + by * by), cx * cx + cy * cy);
+    const float cr = fabsf(ax * by - ay * bx);
+    float rho = lod_scale * (float)R0 * sqrtf(e2) / cr;
+    int l = 0;
+    while (rho >= 2.f && l < levels - 1) { rho *= 0.5f; ++l; }
+    t = l < levels - 1 ? fminf(fmaxf(rho - 1.f, 0.f), 1.f) : 0.f;
+    return l;
+}
+
+// M3: the colour of face f of a pyramid [levels][F,S(R0 >> l),3] at level l and the barycentrics (., b1, b2), blended by t towards level
+// l + 1; t == 0 reads one level and gives lattice_colour's own bits on it
+__device__ __forceinline__ void pyramid_colour(const float* __restrict__ pyramid, int F, int f, int R0, int l, float t, float b1, float b2, float c[3]) {
+    const int R = R0 >> l, S = (R + 1) * (R + 2) / 2;
+    const float* level = pyramid + 3 * ((size_t)F * pyramid_nodes_before(R0, l));
+    lattice_colour(level + 3 * ((size_t)f * S), R, b1, b2, c);
+    if (t > 0.f) {
+        const int Rc = R >> 1;
+        float d[3];
+        lattice_colour(level + 3 * ((size_t)F * S) + 3 * ((size_t)f * ((Rc + 1) * (Rc + 2) / 2)), Rc, b1, b2, d);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = c[k] + t * (d[k] - c[k]);
+    }
+}
+
 }  // namespace nm_rast
 
 struct nm_raster_s {

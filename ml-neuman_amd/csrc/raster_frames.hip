@@ -22,6 +22,11 @@
 // a template argument; every other kernel and the host code serve both entries.  The lattice stays [F,S,3] as the caller made it: a pixel
 // reads three nodes of 12 bytes inside its face's 12 S bytes, neighbouring pixels of a face read the same or neighbouring nodes, so a wave's
 // nine loads fall into a few cache lines that the tile's other waves and the next frames' tiles find in L2.
+//
+// nm_raster_frames_lattice_mip is the same call again with rule F2'' ('mesh mip', rules M2 and M3; raster_device.h's lattice_level and
+// pyramid_colour): the colour comes from a pyramid of the lattice (mesh_lattice.hip), at a level chosen per frame and face from the winner's
+// three screen vertices -- the ones the depth test read -- and blended towards the next coarser level.  The colour source is a three-valued
+// template argument; a pixel reads three nodes of one level or of two.
 #include "raster_device.h"
 
 namespace {
@@ -33,7 +38,9 @@ constexpr int kScanThreads = 1024;           // the one workgroup of frames_scan
 struct Frames {
     int B, V, F, W, H, TX, T;
     int lit;                                 // normals and light were given
-    int R;                                   // the colour lattice's resolution (frames_tile_kernel<true>), else 0
+    int R;                                   // the colour lattice's resolution (level 0's for a pyramid), else 0
+    int levels;                              // the pyramid's levels (frames_tile_kernel<kPyramid>), else 0
+    float lod_scale;                         // rule M2's factor
     float light[3];                          // world space
 };
 
@@ -118,8 +125,11 @@ __device__ __forceinline__ void face_record(const float4* __restrict__ vs, const
 // rule F5's byte: truncation; fmaxf returns its other operand for a NaN, so a NaN gives 0
 __device__ __forceinline__ uint8_t colour_byte(float c) { return (uint8_t)fminf(fmaxf(c * 255.f, 0.f), 255.f); }
 
-// kLattice = false: `colours` is [V,3], rule F2 (null: white); true: `colours` is the faces' lattice [F,S,3] of resolution fr.R, rule F2'
-template <bool kLattice>
+// the colour source.  kVertex: `colours` is [V,3], rule F2 (null: white); kLattice: `colours` is the faces' lattice [F,S,3] of resolution
+// fr.R, rule F2'; kPyramid: `colours` is that lattice's pyramid of fr.levels levels, rule F2''
+enum Source { kVertex = 0, kLattice = 1, kPyramid = 2 };
+
+template <int kSource>
 __global__ void __launch_bounds__(kBatch) frames_tile_kernel(const float4* __restrict__ vscr, const int32_t* __restrict__ faces, const int64_t* __restrict__ offset,
                                                             const int32_t* __restrict__ list, const float* __restrict__ verts,
                                                             const float* __restrict__ colours, const float* __restrict__ normals, Frames fr,
@@ -150,8 +160,8 @@ __global__ void __launch_bounds__(kBatch) frames_tile_kernel(const float4* __res
     if (col >= fr.W || row >= fr.H) return;
     const size_t p = (size_t)b * fr.W * fr.H + (size_t)row * fr.W + col;
     float b0 = 0.f, b1 = 0.f, b2 = 0.f;
+    float4 r0, r1;                                             // the winner's record: kPyramid reads its screen vertices again below
     if (fmin >= 0) {
-        float4 r0, r1;
         float iz2;
         face_record(vs, faces, fmin, r0, r1, iz2);
         winner_bary(r0, r1, iz2, px, py, b0, b1, b2);
@@ -167,7 +177,11 @@ __global__ void __launch_bounds__(kBatch) frames_tile_kernel(const float4* __res
     }
     const int i0 = faces[3 * fmin], i1 = faces[3 * fmin + 1], i2 = faces[3 * fmin + 2];
     float c[3] = {1.f, 1.f, 1.f};                               // F2: no colours is white itself, not a blend of ones
-    if (kLattice) {                                            // F2': rule L3 at the winner's b'
+    if (kSource == kPyramid) {                                 // F2'': rule M2's level of this frame's face, rule M3 at the winner's b'
+        float t;
+        const int l = lattice_level(r0, r1, fr.R, fr.levels, fr.lod_scale, t);
+        pyramid_colour(colours, fr.F, fmin, fr.R, l, t, b1, b2, c);
+    } else if (kSource == kLattice) {                          // F2': rule L3 at the winner's b'
         lattice_colour(colours + (size_t)fmin * (size_t)(3 * ((fr.R + 1) * (fr.R + 2) / 2)), fr.R, b1, b2, c);
     } else if (colours) {
 #pragma unroll
@@ -214,9 +228,10 @@ int reserve_frames(nm_raster_s* h, int B, int T) {
     return NM_OK;
 }
 
-// both entries: R = 0 is nm_raster_frames (colours [V,3], nullable), R >= 1 nm_raster_frames_lattice (colours [F,S,3])
+// the three entries: R = 0 is nm_raster_frames (colours [V,3], nullable), R >= 1 and levels = 0 nm_raster_frames_lattice (colours [F,S,3]),
+// levels >= 1 nm_raster_frames_lattice_mip (colours the pyramid of a lattice of resolution R)
 int raster_frames(const char* who, nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H, const float* colours, int R,
-                  const float* normals, const double* light, const uint8_t* bg, const float* bg_z, uint8_t* out, int32_t* face_id, float* zbuf,
+                  int levels, float lod_scale, const float* normals, const double* light, const uint8_t* bg, const float* bg_z, uint8_t* out, int32_t* face_id, float* zbuf,
                   float* bary, nm_stream_t stream) {
     NM_REQUIRE(B >= 1 && B <= 65535, "%s: B = %d frames (1 <= B <= 65535)", who, B);
     NM_REQUIRE(W >= 1 && H >= 1 && (int64_t)W * H <= (1ll << 30), "%s: bad image size W=%d H=%d", who, W, H);
@@ -230,6 +245,8 @@ int raster_frames(const char* who, nm_raster_t h, const float* verts, const doub
     fr.T = fr.TX * ((H + kTile - 1) / kTile);
     fr.lit = normals ? 1 : 0;
     fr.R = R;
+    fr.levels = levels;
+    fr.lod_scale = lod_scale;
     for (int k = 0; k < 3; ++k) fr.light[k] = light ? (float)light[k] : 0.f;
     const int64_t n = (int64_t)B * fr.T;
     int rc = NM_OK;
@@ -250,11 +267,14 @@ int raster_frames(const char* who, nm_raster_t h, const float* verts, const doub
         nm::set_error("%s: bad list total %lld", who, (long long)total); return NM_ERR_UNSUPPORTED; }
     if ((rc = reserve_lists(h, total))) return rc;
     if (total > 0) hipLaunchKernelGGL(frames_bin_kernel<true>, per_face, dim3(256), 0, st, h->d_fvscr, h->d_faces, fr, h->d_fcount, h->d_foffset, h->d_list, total);
-    if (R > 0)
-        hipLaunchKernelGGL(frames_tile_kernel<true>, dim3(fr.T, B), dim3(kBatch), 0, st, h->d_fvscr, h->d_faces, h->d_foffset, h->d_list, verts, colours, normals, fr,
+    if (levels > 0)
+        hipLaunchKernelGGL(frames_tile_kernel<kPyramid>, dim3(fr.T, B), dim3(kBatch), 0, st, h->d_fvscr, h->d_faces, h->d_foffset, h->d_list, verts, colours, normals, fr,
+                           bg, bg_z, out, face_id, zbuf, bary);
+    else if (R > 0)
+        hipLaunchKernelGGL(frames_tile_kernel<kLattice>, dim3(fr.T, B), dim3(kBatch), 0, st, h->d_fvscr, h->d_faces, h->d_foffset, h->d_list, verts, colours, normals, fr,
                            bg, bg_z, out, face_id, zbuf, bary);
     else
-        hipLaunchKernelGGL(frames_tile_kernel<false>, dim3(fr.T, B), dim3(kBatch), 0, st, h->d_fvscr, h->d_faces, h->d_foffset, h->d_list, verts, colours, normals, fr,
+        hipLaunchKernelGGL(frames_tile_kernel<kVertex>, dim3(fr.T, B), dim3(kBatch), 0, st, h->d_fvscr, h->d_faces, h->d_foffset, h->d_list, verts, colours, normals, fr,
                            bg, bg_z, out, face_id, zbuf, bary);
     if ((rc = nm::check_launch("nm_raster_frames: frames_tile_kernel"))) return rc;
     // (the bad frame's outputs are defined all the same: its lists are empty, so face_id -1, zbuf +inf and out the background)
@@ -270,7 +290,7 @@ int nm_raster_frames(nm_raster_t h, const float* verts, const double* w2c, const
                      const float* normals, const double* light, const uint8_t* bg, const float* bg_z, uint8_t* out, int32_t* face_id, float* zbuf,
                      float* bary, nm_stream_t stream) {
     NM_REQUIRE(h && verts && w2c && intr && out, "nm_raster_frames: null pointer");
-    return raster_frames("nm_raster_frames", h, verts, w2c, intr, B, W, H, colours, 0, normals, light, bg, bg_z, out, face_id, zbuf, bary, stream);
+    return raster_frames("nm_raster_frames", h, verts, w2c, intr, B, W, H, colours, 0, 0, 0.f, normals, light, bg, bg_z, out, face_id, zbuf, bary, stream);
 }
 
 int nm_raster_frames_lattice(nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H, const float* face_colours,
@@ -278,7 +298,19 @@ int nm_raster_frames_lattice(nm_raster_t h, const float* verts, const double* w2
                              float* zbuf, float* bary, nm_stream_t stream) {
     NM_REQUIRE(h && verts && w2c && intr && out && face_colours, "nm_raster_frames_lattice: null pointer");
     NM_REQUIRE(R >= 1 && R <= 64, "nm_raster_frames_lattice: R = %d (1 <= R <= 64)", R);
-    return raster_frames("nm_raster_frames_lattice", h, verts, w2c, intr, B, W, H, face_colours, R, normals, light, bg, bg_z, out, face_id, zbuf, bary, stream);
+    return raster_frames("nm_raster_frames_lattice", h, verts, w2c, intr, B, W, H, face_colours, R, 0, 0.f, normals, light, bg, bg_z, out, face_id, zbuf, bary, stream);
+}
+
+int nm_raster_frames_lattice_mip(nm_raster_t h, const float* verts, const double* w2c, const double* intr, int B, int W, int H, const float* pyramid, int R0,
+                                 int levels, float lod_scale, const float* normals, const double* light, const uint8_t* bg, const float* bg_z, uint8_t* out,
+                                 int32_t* face_id, float* zbuf, float* bary, nm_stream_t stream) {
+    NM_REQUIRE(h && verts && w2c && intr && out && pyramid, "nm_raster_frames_lattice_mip: null pointer");
+    NM_REQUIRE(R0 >= 1 && R0 <= 64, "nm_raster_frames_lattice_mip: R0 = %d (1 <= R0 <= 64)", R0);
+    NM_REQUIRE(levels >= 1 && levels <= 7 && (R0 & ((1 << (levels - 1)) - 1)) == 0, "nm_raster_frames_lattice_mip: levels = %d (>= 1, and 2^(levels-1) divides R0 = %d)",
+               levels, R0);
+    NM_REQUIRE(isfinite(lod_scale) && lod_scale >= 0.f, "nm_raster_frames_lattice_mip: lod_scale = %g (finite, >= 0)", (double)lod_scale);
+    return raster_frames("nm_raster_frames_lattice_mip", h, verts, w2c, intr, B, W, H, pyramid, R0, levels, lod_scale, normals, light, bg, bg_z, out, face_id, zbuf,
+                         bary, stream);
 }
 
 }  // extern "C"

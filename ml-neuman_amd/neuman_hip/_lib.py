@@ -227,6 +227,10 @@ SIGNATURES = {
     "nm_mesh_lattice_rows": (i32, [c_i32p, i64, i64, c_f32p, i32, i32, c_f32p, c_stream]),
     "nm_raster_frames_lattice": (i32, [ctypes.c_void_p, c_f32p, ctypes.c_void_p, ctypes.c_void_p, i32, i32, i32, c_f32p, i32, c_f32p,
                                        ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, c_f32p, ctypes.c_void_p, c_i32p, c_f32p, c_f32p, c_stream]),
+    "nm_mesh_lattice_pyramid_size": (i32, [i32, i32, ctypes.POINTER(i64)]),
+    "nm_mesh_lattice_pyramid": (i32, [c_f32p, i64, i32, i32, i32, c_f32p, c_stream]),
+    "nm_raster_frames_lattice_mip": (i32, [ctypes.c_void_p, c_f32p, ctypes.c_void_p, ctypes.c_void_p, i32, i32, i32, c_f32p, i32, i32, ctypes.c_float, c_f32p,
+                                           ctypes.POINTER(ctypes.c_double), ctypes.c_void_p, c_f32p, ctypes.c_void_p, c_i32p, c_f32p, c_f32p, c_stream]),
     "nm_mesh_atlas_size": (i32, [i64, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
     "nm_mesh_atlas_pack": (i32, [c_f32p, i64, i32, c_f32p, c_stream]),
     "nm_mesh_atlas_sample": (i32, [c_f32p, i64, i32, c_i32p, c_f32p, i64, c_f32p, c_stream]),

@@ -180,20 +180,25 @@ class Rasterizer:
         return g_verts
 
     def render_frames(self, verts, cameras, colours=None, normals=None, light=LIGHT, background=None, background_z=None, want_geometry=False, out=None, *,
-                      face_colours=None):
+                      face_colours=None, lod_scale=None):
         """nm_raster_frames (the header's 'mesh frames', rules F1-F7): B frames of the mesh as images, one call and one host read -> out uint8
         [B,H,W,3], or (out, face_id [B,H,W] int32, zbuf [B,H,W] f32, bary [B,H,W,3] f32) with want_geometry; frame b's geometry is the bits
         `rasterize` gives on frame b.  verts [B,V,3]; `cameras` as `batch_cameras` makes them; colours [V,3] f32 (None: white); normals
         [B,V,3] f32 switch the diffuse light at `light` on; background uint8 [B,H,W,3] (None: white); background_z f32 [B,H,W], camera-space
         depth the mesh must be nearer than.  `out`: a dense uint8 [B,H,W,3] tensor on verts' device to write into instead of a new one.
         face_colours [F,S,3] f32, a colour lattice as `mesh_texture.bake_face_colours` makes it, in place of `colours` (ValueError for both):
-        nm_raster_frames_lattice (the header's 'mesh lattice', rule F2'), the resolution recovered from S; the geometry is the same bits."""
+        nm_raster_frames_lattice (the header's 'mesh lattice', rule F2'), the resolution recovered from S; the geometry is the same bits.
+        face_colours a `mesh_texture.LatticePyramid`: nm_raster_frames_lattice_mip (the header's 'mesh mip', rule F2''), which filters under
+        minification: a level per frame and face from the face's size on the screen, two levels blended.  lod_scale (default 1.0; finite,
+        >= 0) scales the nodes-per-pixel figure the level comes from: 0 is the plain lattice, larger is blurrier.  lod_scale without a
+        pyramid is a ValueError."""
         who = "render_frames"
         if colours is not None and face_colours is not None:
             raise ValueError(f"{who}: give colours (one per vertex) or face_colours (a lattice per face), not both")
+        pyramid, face_colours = pyramid_of(face_colours, lod_scale, self.F, who)
         verts, w2c, intr, B, W, H = self._batch(verts, cameras, who)
         dev = verts.device
-        R = None if face_colours is None else lattice_resolution_of(face_colours, self.F, who)
+        R = None if face_colours is None else pyramid.R if pyramid is not None else lattice_resolution_of(face_colours, self.F, who)
 
         def dense(t, name, dtype, shape):
             if t is None:
@@ -225,9 +230,28 @@ class Rasterizer:
                     _lib.dev_ptr(face_id, torch.int32), _lib.dev_ptr(zbuf), _lib.dev_ptr(bary), _lib.stream_ptr())
             if face_colours is None:
                 _lib.check(_lib.lib().nm_raster_frames(*head, _lib.dev_ptr(colours), *tail), "nm_raster_frames")
+            elif pyramid is not None:
+                _lib.check(_lib.lib().nm_raster_frames_lattice_mip(*head, _lib.dev_ptr(face_colours), R, pyramid.levels, 1.0 if lod_scale is None else lod_scale,
+                                                                   *tail), "nm_raster_frames_lattice_mip")
             else:
                 _lib.check(_lib.lib().nm_raster_frames_lattice(*head, _lib.dev_ptr(face_colours), R, *tail), "nm_raster_frames_lattice")
         return (out, face_id, zbuf, bary) if want_geometry else out
+
+
+def pyramid_of(face_colours, lod_scale, n_faces, who):
+    """-> (the `mesh_texture.LatticePyramid` or None, the tensor the entry reads: the pyramid's flat buffer, or face_colours as it came).
+    ValueError for a lod_scale without a pyramid or one that is no number; NeumanHipError for a pyramid of another mesh or not of colours"""
+    from .mesh_texture import LatticePyramid
+    if not isinstance(face_colours, LatticePyramid):
+        if lod_scale is not None:
+            raise ValueError(f"{who}: lod_scale goes with a LatticePyramid (mesh_texture.lattice_pyramid), not with "
+                             f"{'a plain lattice' if face_colours is not None else 'no face_colours'}")
+        return None, face_colours
+    if lod_scale is not None and (isinstance(lod_scale, bool) or not isinstance(lod_scale, (int, float, np.integer, np.floating))):
+        raise ValueError(f"{who}: lod_scale must be a number, got {lod_scale!r}")
+    if face_colours.F != n_faces or face_colours.w != 3:
+        raise _lib.NeumanHipError(f"{who}: face_colours must be the pyramid of a [{n_faces}, S, 3] lattice, got one of a [{face_colours.F}, S, {face_colours.w}] lattice")
+    return face_colours, face_colours.data
 
 
 def lattice_resolution_of(face_colours, n_faces, who):

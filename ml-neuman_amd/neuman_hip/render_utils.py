@@ -1476,7 +1476,7 @@ def depth_to_camera_z(depth, cap):
 
 
 def render_mesh_frames(world_verts, faces, caps, colours=None, normals=None, background=None, background_depth=None, light=None, frames_per_call=None, *,
-                       face_colours=None):
+                       face_colours=None, lod_scale=None):
     """The frames of a posed mesh as images -> uint8 [B,H,W,3] on the device.  world_verts [B,V,3] and normals [B,V,3] (optional: they switch
     the diffuse light on) as `mesh_pose.pose_mesh_frames` returns them, faces [F,3], colours [V,3] float32 as `mesh_extract.extract_net_mesh`
     returns them (None: white); caps the B captures (one image size; ValueError otherwise) or what `raster.batch_cameras` made of them.
@@ -1486,11 +1486,15 @@ def render_mesh_frames(world_verts, faces, caps, colours=None, normals=None, bac
     device and is taken as it is: nothing is converted.  The sequence goes through nm_raster_frames `frames_per_call` frames at a time
     (default: `mesh_frames_per_call`), every call writing its frames straight into the result, which does not depend on the chunking.
     face_colours [F,S,3] float32: a colour lattice of the canonical mesh as `mesh_texture.bake_face_colours` makes it, in place of `colours`
-    (ValueError for both): every frame is shaded from it (nm_raster_frames_lattice; the header's 'mesh lattice')."""
+    (ValueError for both): every frame is shaded from it (nm_raster_frames_lattice; the header's 'mesh lattice').  face_colours a
+    `mesh_texture.LatticePyramid` (`mesh_texture.lattice_pyramid` of such a lattice): the frames are filtered under minification
+    (nm_raster_frames_lattice_mip; the header's 'mesh mip'), every face at the level its size in that frame asks for; lod_scale (default
+    1.0, finite and >= 0; larger is blurrier, 0 the plain lattice) goes with a pyramid only (ValueError otherwise)."""
     from . import raster
     who = "render_mesh_frames"
     if colours is not None and face_colours is not None:
         raise ValueError(f"{who}: give colours (one per vertex) or face_colours (a lattice per face), not both")
+    pyramid, _ = raster.pyramid_of(face_colours, lod_scale, len(faces), who)
 
     def dense(t, name, dtype, shapes):
         if t is None:
@@ -1514,7 +1518,9 @@ def render_mesh_frames(world_verts, faces, caps, colours=None, normals=None, bac
     if tuple(w2c.shape) != (B, 4, 4) or tuple(intr.shape) != (B, 4):
         raise _lib.NeumanHipError(f"{who}: {w2c.shape[0]} cameras for {B} frames")
     colours = dense(colours, "colours", torch.float32, [(V, 3)])
-    if face_colours is not None:
+    if pyramid is not None:
+        dense(pyramid.data, "face_colours.data", torch.float32, [tuple(pyramid.data.shape)])
+    elif face_colours is not None:
         raster.lattice_resolution_of(face_colours, len(faces), who)
         face_colours = dense(face_colours, "face_colours", torch.float32, [tuple(face_colours.shape)])
     normals = dense(normals, "normals", torch.float32, [(B, V, 3)])
@@ -1537,5 +1543,5 @@ def render_mesh_frames(world_verts, faces, caps, colours=None, normals=None, bac
             bg = None if background is None else (shared[:b1 - b0] if shared is not None else background[b0:b1])
             bg_z = None if background_depth is None else torch.stack([depth_to_camera_z(background_depth[b], caps[b]) for b in range(b0, b1)])
             rast.render_frames(world_verts[b0:b1], (w2c[b0:b1], intr[b0:b1], W, H), colours, None if normals is None else normals[b0:b1], light, bg, bg_z,
-                               out=out[b0:b1], face_colours=face_colours)
+                               out=out[b0:b1], face_colours=face_colours, lod_scale=lod_scale)
     return out
