@@ -730,7 +730,8 @@ int nm_shot_rays_cams(const int32_t* xy, const int32_t* cam_id, int64_t n, int m
  *   renderer's f32 [H,W,3] frame) and render_test_views.py:35 (PSNR of the uint8 frames).
  *   imageio is a conda dependency (environment.yml:22, unpinned), not vendored: nm_frame_to_uint8
  *   restates its published float -> uint8 rule (v2 image_as_uint: clip to [0,1], x*255 + 0.499999999,
- *   truncate).  nm_ssd_u8 returns the exact integer sum of squared differences of two uint8 arrays;
+ *   truncate; -inf gives 0, +inf 255, and a NaN gives 0, as rule F5 of the mesh frames has it).
+ *   nm_ssd_u8 returns the exact integer sum of squared differences of two uint8 arrays;
  *   PSNR = 10 log10(255^2 * n / ssd) is skimage.metrics.peak_signal_noise_ratio (environment.yml:30)
  *   for uint8 inputs.  ssd: device uint64[1].
  * ------------------------------------------------------------------------------------------- */
@@ -1456,7 +1457,11 @@ int nm_composite_backward(const float* raw, const float* z_vals, const float* ra
  *                     (the symmetry term, :292-304); da_raw / db_raw [n][4]
  *   nm_loss_shape: the SMPL shape prior (:305-343): w_smpl * mean_{dist_h < 0}((1 - occ(pred))^2) + w_dummy * (mean_{dist_d < 0}((1 - occ(dummy))^2)
  *                  + mean_{dist_d > 0}(|occ(dummy) * (|dist_d| * outside_factor)^exponent|)), occ = 1 - exp(-relu(sigma)), empty selections count as 1;
- *                  nd = 0: the first term alone; norm3: three device floats of scratch */
+ *                  nd = 0: the first term alone; norm3: three device floats, left holding weight / max(count, 1) of the three selections.
+ * Gradients are autograd's on these formulas in float32, kinks included: relu passes nothing at sigma <= 0, clamp passes inside the closed interval,
+ * abs has slope 0 at 0 -- so the outside term's gradient is exactly 0 wherever occ(dummy) * (|dist_d| * outside_factor)^exponent is 0 in float32
+ * (sigma below about 3e-8).  A NaN density reaches the value of every term that reads it; a NaN distance is in no selection.  Columns a term does
+ * not read get gradient 0 whatever they hold.  The result is the same bits on every run, whatever the workspace held before. */
 int64_t nm_loss_workspace_doubles(void);
 int nm_loss_bimodal(const float* x, int64_t n, int clamp01, float offset, float* loss, float* dx, double* workspace, nm_stream_t stream);
 int nm_loss_pair_mse(int mode, const float* a_raw, const float* b_raw, int64_t n, float scale, float* loss, float* da_raw, float* db_raw,

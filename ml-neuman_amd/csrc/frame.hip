@@ -84,10 +84,10 @@ __global__ __launch_bounds__(256) void shot_rays_cams_kernel(const int32_t* __re
     shoot((double)xy[2 * i], (double)xy[2 * i + 1], P, P + 9, mode, origin + 3 * i, direction + 3 * i);
 }
 
-// imageio (v2 `image_as_uint`, bitdepth 8) on a float image: clip to [0, 1], then uint8(x * 255 + 0.499999999) in f64
+// imageio (v2 `image_as_uint`, bitdepth 8) on a float image: clip to [0, 1], then uint8(x * 255 + 0.499999999) in f64; a NaN gives 0
 __device__ __forceinline__ uint8_t to_uint8(float x) {
     double v = (double)x;
-    v = v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v);                   // NaN falls through both comparisons and converts to 0
+    v = v != v ? 0.0 : (v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v));  // the NaN is named: converting one to an integer is undefined
     return (uint8_t)(int)(v * 255.0 + 0.499999999);
 }
 __global__ __launch_bounds__(256) void to_uint8_kernel(const float* __restrict__ src, int64_t n, uint8_t* __restrict__ dst) {
@@ -162,10 +162,17 @@ __global__ __launch_bounds__(256) void ssim_partial_kernel(const uint8_t* __rest
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = (part[0] + part[1]) + (part[2] + part[3]);
 }
-__global__ void ssim_final_kernel(const double* __restrict__ partial, int blocks, double n, double* __restrict__ out) {
+// The mean from the partials, by one workgroup: thread t adds partials t, t + 256, ... in order and the 256 sums are added in a fixed tree -- the same
+// order on every run, and a rounding error that does not grow with the number of partials (one thread adding 4096 in turn drifted by up to 1e-13)
+__global__ __launch_bounds__(256) void ssim_final_kernel(const double* __restrict__ partial, int blocks, double n, double* __restrict__ out) {
     double s = 0.0;
-    for (int i = 0; i < blocks; ++i) s += partial[i];
-    out[0] = s / n;
+    for (int i = threadIdx.x; i < blocks; i += 256) s += partial[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+    __shared__ double part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = ((part[0] + part[1]) + (part[2] + part[3])) / n;
 }
 
 }  // namespace
@@ -236,7 +243,7 @@ int nm_ssim_u8(const uint8_t* a, const uint8_t* b, int H, int W, int C, double* 
     const int64_t n = (int64_t)(H - 2 * kSsimPad) * (W - 2 * kSsimPad) * C;
     const int blocks = (int)((n + 255) / 256 < NM_SSIM_WORKSPACE_DOUBLES ? (n + 255) / 256 : NM_SSIM_WORKSPACE_DOUBLES);
     hipLaunchKernelGGL(ssim_partial_kernel, dim3(blocks), dim3(256), 0, st, a, b, H, W, C, workspace);
-    hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(1), 0, st, workspace, blocks, (double)n, ssim);
+    hipLaunchKernelGGL(ssim_final_kernel, dim3(1), dim3(256), 0, st, workspace, blocks, (double)n, ssim);
     return nm::check_launch("ssim kernels");
 }
 

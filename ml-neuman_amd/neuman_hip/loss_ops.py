@@ -21,9 +21,9 @@ def _ws(dev):
 
 
 def _rows(raw):
-    r = raw.reshape(-1, 4)
-    if r.dtype != torch.float32 or not r.is_contiguous() or (r.data_ptr() & 15):
-        r = r.to(torch.float32).contiguous()
+    r = raw.reshape(-1, 4).to(torch.float32).contiguous()
+    if r.data_ptr() & 15:                    # a dense view comes back from .contiguous() as it is, wherever it starts: the kernels read whole rows
+        r = r.clone()
     return r
 
 
