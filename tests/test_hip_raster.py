@@ -6,7 +6,11 @@ Tolerances on values are calibrated at run time: the helper also runs in float32
 from the float64 run on the same input (floor: 1e-6 relative) -- four is the margin for a different but equally valid float32 evaluation order.
 Face ids are compared exactly, except on the pixels the float64 run itself calls ambiguous (a pixel centre within 1e-4, in barycentrics, of an
 edge of a face that is not more than 0.1 % behind the winner, or two covering depths within 1e-4 relative); those are at most 1 % of the covered
-pixels.  The measured deviations are printed ([raster] lines; profiles/raster.md keeps a copy)."""
+pixels.  The measured deviations are printed ([raster] lines; profiles/raster.md keeps a copy).
+
+The ambiguous pixels left out here -- centres on an edge or a vertex, exact depth ties -- are what tests/test_hip_raster_exact.py is about: on
+the quarter-pixel scenes of tests/helpers/raster_exact.py every float32 operand is exact, and ids, depth and barycentrics are compared at every
+pixel with no tolerance and no exclusions."""
 import ctypes
 import os
 import sys
